@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
 """bench.py — seed vertices/sec through the MI355X block finder (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ecoli62|ecoli10|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ecoli62|ecoli10|...] [--dump-outputs DIR] [--full]
 
 A "step" is one full pass of the hot path over the workload's sorted seed list: BlocksFinder::FindBlocks' phase loop
 (every seed through the per-seed HIP kernels, ordered commit, GPU re-processing of conflicts) with the junction tables
-already resident in HBM. value = seeds / step time (whole job over all GPUs).
+already resident in HBM. value = seeds / step time (whole job over all GPUs); ms_per_step = milliseconds of one timed step.
 
 Workload at N = 1: the largest single-GPU configuration of BASELINE.json, configs[2] "62 E. coli strains, k=15", restated
 as the synthetic pangenome of SURVEY.md §8d at its stated size (62 strains, 281 Mbp, lcb-synth seed 1002 + lcb-mkgraph,
 untimed; there are no genomes and no network here). `--workload ecoli10` is configs[1] (10 strains, 45 Mbp).
 
-The JSON line also carries
+A plain run sets up (the workload's files are generated once and kept in $LCB_BENCH_DIR), warms up, times K steps and prints
+one JSON line: the headline figure and the engine's statistics of the last step (`config`). `--dump-outputs DIR` writes what
+the last timed step returned to its caller, as float64 .npy files: blocks.npy (one row per block instance: id, chr, start, end,
+in the engine's order) and counts.npy (blocks found, commit conflicts). The inputs are generated from fixed seeds, so two
+builds given the same arguments can be compared file for file.
+
+`--full` adds everything the headline figure does not need, each part bounded so that the whole run stays within
+--full-budget seconds (parts that no longer fit are reported as skipped). The line of a --full run also carries
   roofline      the process kernels (lcb_process_kernel, all variants): ALGORITHMIC bytes per launch (SURVEY.md §8d formula
                 over the reference-semantics event counters, counted by the kernels themselves in one untimed stats-mode pass of
                 the engine) / average launch duration, measured in this run with HIP events on the kernels' stream; against the
@@ -25,6 +32,7 @@ The JSON line also carries
                 3, banner to banner, at -t 1, -t 64 and -t <all hardware threads>. `--sample-cpu-baseline` skips the whole-workload
                 run (the round-2 protocol).
   wall_clock    metric part 2: the whole sibeliaz-lcb process (load, seeds, upload, phase loop, GFF) on the workload.
+  secondary     (default workload) the k = 25 shapes of configs 4 / 5 at test size, each timed by a child `bench.py --full --secondary-leg`.
 N > 1: either under torch.distributed.run (one rank per GPU: torch only ships the RCCL unique id and takes the max of the step
 times) or called directly (`python bench.py --gpus N`): one process, a persistent lcb_gpus set - one host thread per GPU inside the
 library, ncclCommInitAll. Either way the all-gathers of the engine are ncclAllGather calls inside the C++ library (csrc/comm.hip).
@@ -37,6 +45,8 @@ import statistics
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -102,6 +112,8 @@ SAMPLES = {"ecoli62": ("ecoli62_small", "ecoli62_tiny"), "ecoli10": ("ecoli10", 
            # is the workload itself
            "primates8_test": ("primates8_test", "primates8_tiny"), "mice16_test": ("mice16_test", "mice16_tiny")}
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8 TB/s
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+REF_EXE = os.path.join(ROOT, "oracle", "_ref", "sibeliaz-lcb-ref")      # the unmodified reference (--full: cpu_baseline)
 
 
 def log(*a):
@@ -137,11 +149,10 @@ def run_reference(w, threads, tag, limit_s=None):
     """One run of the unmodified reference: (analyze seconds banner to banner, whole-process seconds, gff path); None if it is not
     there or failed; the string "timeout" if it ran longer than limit_s (it is killed: every leg of the protocol is bounded)."""
     import threading
-    ref = os.path.join(ROOT, "oracle", "_ref", "sibeliaz-lcb-ref")
-    if not os.path.exists(ref):
+    if not os.path.exists(REF_EXE):
         return None
     out = os.path.join(w["dir"], "ref_out_%s" % tag)
-    cmd = [ref, "--graph", w["graph"], w["fasta"], "-k", str(w["k"]), "-b", str(w["b"]), "-m", str(w["m"]), "-a", str(w["a"]), "-t", str(threads),
+    cmd = [REF_EXE, "--graph", w["graph"], w["fasta"], "-k", str(w["k"]), "-b", str(w["b"]), "-m", str(w["m"]), "-a", str(w["a"]), "-t", str(threads),
            "-o", out, "--noseq"]
     t0 = time.time()
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, bufsize=0)
@@ -210,16 +221,26 @@ def cpu_baseline_quick(workload, threads, our_gff_path, limit_s=120.0):
                       "%.2f s (includes its serial seed enumeration), whole process %.2f s; host has %d hardware threads" % (whole["desc"], t32, r[0], r[1], host)}
 
 
-def secondary_live(names, threads, no_cpu=False):
-    """The other shapes of BASELINE.json, timed by THIS run: `bench.py --workload <name> --steps 3 --warmup 1 --secondary-leg` as a child process each
-    (its own device and tables; the parent's are closed by then), its line condensed into one entry."""
+def secondary_live(names, threads, no_cpu=False, deadline=None):
+    """The other shapes of BASELINE.json, timed by THIS run: `bench.py --full --workload <name> --steps 3 --warmup 1 --secondary-leg` as a child process
+    each (its own device and tables; the parent's are closed by then), its line condensed into one entry. deadline (time.time() value): a child
+    that cannot get a minute before it is skipped, and it is given what is left as its own budget and time limit."""
     out = []
     for name in names:
         t = time.time()
+        left = 420.0 if deadline is None else min(420.0, deadline - t)
+        if left < 60.0:
+            out.append({"workload": name, "measured_in_this_run": False, "skipped": "the budget of the --full run was spent"})
+            continue
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", "3", "--warmup", "1", "--no-cli", "--secondary-leg",
-                                "--threads", str(threads)] + (["--no-cpu-baseline"] if no_cpu else []), capture_output=True, text=True, timeout=420)
+                                "--full", "--full-budget", "%.0f" % left, "--threads", str(threads)] + (["--no-cpu-baseline"] if no_cpu else []),
+                               capture_output=True, text=True, timeout=left)
             line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        except subprocess.TimeoutExpired as e:      # a child cut off by its limit: no further GPU child is started
+            out.append({"workload": name, "measured_in_this_run": True, "error": repr(e)})
+            deadline = t
+            continue
         except Exception as e:       # a secondary entry must never cost the line itself
             out.append({"workload": name, "measured_in_this_run": True, "error": repr(e)})
             continue
@@ -318,12 +339,32 @@ def algorithmic_bytes(c):
     return 9 * c["n_walk"] + 15 * c["n_occ"] + 16 * c["n_compat_call"] + c["n_compat_step"] + 13 * c["n_inst_out"]
 
 
+def dump_outputs(out_dir, blocks, stats):
+    """What the last timed step returned to its caller, as float64 (exact: ids, chromosomes and positions are below 2^53): the block list
+    (id, chr, start, end per instance, in the engine's order) and the two result counts. A list larger than DUMP_MAX_BYTES is reduced to a
+    fixed, seeded sample of its rows, whose indices go to blocks_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    b = np.stack([blocks[f].astype(np.float64) for f in ("id", "chr", "start", "end")], axis=1) if len(blocks) else np.zeros((0, 4), np.float64)
+    if b.nbytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(b), DUMP_MAX_BYTES // (2 * b.itemsize * b.shape[1]), replace=False))
+        b = b[rows]
+        np.save(os.path.join(out_dir, "blocks_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "blocks.npy"), b)
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([stats["blocks_found"], stats["failures"]], dtype=np.float64))
+
+
 def main():
+    t_start = time.time()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (passes over the workload)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="ecoli62")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the block list and result counts of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also the roofline (event counts, STREAM triad), the whole-process wall clock, the reference's CPU "
+                    "baseline and the secondary shapes; the options below that name them apply to a --full run")
+    ap.add_argument("--full-budget", type=float, default=540.0, help="seconds a --full run may take from start to exit: every part after the timed steps "
+                    "is bounded by what is left of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sample-cpu-baseline", action="store_true", help="time the reference on the bounded samples only (not on the whole workload)")
     ap.add_argument("--cpu-baseline-budget", type=float, default=360.0, help="seconds all legs of the reference protocol may take together (every leg is cut off at what is left)")
@@ -339,6 +380,9 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the live lines of the k = 25 shapes (configs 4 / 5 at test size) that a default run appends")
     ap.add_argument("--secondary-leg", action="store_true", help="(internal) this process times one `secondary` entry: one bounded reference leg, no entries of its own")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    deadline = t_start + args.full_budget
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -435,79 +479,9 @@ def main():
         blocks, st = last
         ms_per_step = 1000.0 * elapsed / args.steps
         value = S / (elapsed / args.steps)
-        # parity artefact of the timed run: GFF through the product's GenerateOutput
-        out_dir = os.path.join(w["dir"], "gpu_out")
-        finder.params = params
-        finder.GenerateOutput(out_dir, blocks=blocks, blocks_found=int(st["blocks_found"]))
-        gff = os.path.join(out_dir, "blocks_coords.gff")
-        # algorithmic bytes: one untimed pass of the engine in stats mode; the engine sums the event counters of exactly the
-        # Process() calls the reference makes (phase-start result of every seed + re-processing of every conflict)
-        ctr_file = os.path.join(w["dir"], "counters.json")
-        ctr = None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, blocks, st)
         n_gpus = args.gpus if in_process else world
-        if gpus is not None and not args.no_roofline:
-            # the counting pass and the triad run on one device: a plain one beside the set (the counts do not depend on the GPU count)
-            dev = sibeliaz_amd.Device(storage, params, 0, **dev_opts)
-        if not args.no_roofline:
-            # the counts are a property of (input, parameters): the ones of the named workloads are kept in bench_event_counts.json
-            # (counted by `bench.py --recount` on the MI355X) so that a default run need not repeat the 3-minute counting pass
-            known = json.load(open(os.path.join(ROOT, "bench_event_counts.json"))).get(args.workload) if os.path.exists(os.path.join(ROOT, "bench_event_counts.json")) else None
-            counts_src = None
-            # (--verify-counts counts them again when other sources than the ones of this build counted them)
-            if known and not args.recount and known["lcb_synth"] == w["synth"] and known["seeds"] == S and (known.get("source_hash") == source_hash() or not args.verify_counts):
-                ctr = known["event_counts"]
-                # the counts are a property of (input, parameters), pinned to the CPU oracle at full size; whether the sources of this build are the
-                # ones that last re-counted them on the device is reported, not required
-                counts_src = {"file": "bench_event_counts.json", "counted_by": known.get("source", ""), "source_hash_of_that_build": known.get("source_hash"),
-                              "source_hash_of_this_build": source_hash(), "same_sources": known.get("source_hash") == source_hash()}
-            elif os.path.exists(ctr_file) and not args.recount:
-                ctr = json.load(open(ctr_file))
-            else:
-                t = time.time()
-                dev.set_stats_mode(True)
-                finder.FindBlocks(w["m"], w["b"], device=dev, seeds=seeds, count_events=1)
-                dev.set_stats_mode(False)
-                ctr = {k: int(finder.stats["ev_" + k]) for k in sibeliaz_amd.api.COUNTER_NAMES}
-                json.dump(ctr, open(ctr_file, "w"))
-                if args.write_counts:
-                    allc = json.load(open(os.path.join(ROOT, "bench_event_counts.json"))) if os.path.exists(os.path.join(ROOT, "bench_event_counts.json")) else {}
-                    allc[args.workload] = {"event_counts": ctr, "lcb_synth": w["synth"], "seeds": S, "workload": w["desc"], "source_hash": source_hash(),
-                                           "source": "stats-mode pass of the engine on the MI355X (bench.py --recount --write-counts); reference-semantics counts are a property of input + parameters"}
-                    json.dump(allc, open(os.path.join(ROOT, "bench_event_counts.json"), "w"), indent=1, sort_keys=True)
-                dev.kernel_time()
-                log("bench: stats-mode pass %.1fs: %s" % (time.time() - t, ctr))
-        abytes = algorithmic_bytes(ctr) if ctr else 0
-        kernel_s_per_step = kernel_busy_ms / 1000.0 / args.steps     # GPU time = the union of the kernels' intervals (never more than the step)
-        lps = launches / float(args.steps)
-        achieved = abytes / kernel_s_per_step / 1e9 if kernel_s_per_step > 0 else 0.0
-        triad = dev.hbm_triad() if dev is not None else 0.0
-        # HBM bytes per launch from the PMC counters: collected in separate rocprofv3 --pmc passes of this same command
-        # (scripts/gpu_r2_evidence.sh), committed with the profile summaries; only for the workload they were taken on
-        traffic, traffic_src, pmc = None, None, None
-        pmc_file = next((f for f in (os.path.join(ROOT, "profiles", r, "pmc_traffic.json") for r in ("r06", "r05")) if os.path.exists(f)), None)
-        if args.workload == "ecoli62" and n_gpus == 1 and pmc_file:
-            pmc = json.load(open(pmc_file))
-            traffic = pmc["hbm_bytes_per_launch"]
-            traffic_src = {"file": os.path.relpath(pmc_file, ROOT), "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (separate runs) of `bench.py --steps 1 --warmup 0` on this "
-                           "workload, FETCH_SIZE doubled (gfx950 correction of MI355X_MICROARCH.md), per process-kernel launch",
-                           "source_hash_of_that_build": pmc.get("kernel_source_hash"), "source_hash_of_this_build": source_hash(),
-                           "same_sources": pmc.get("kernel_source_hash") == source_hash()}
-        # per kernel variant: launches and hipEvent-timed kernel time of the timed region (all streams); HBM bytes from the PMC passes where they are of
-        # this build's sources (the reference-semantics event counts are per seed, not per variant: the algorithmic figure stays a whole-pass one)
-        per_kernel = None
-        if mode_t0 is not None and mode_t1 is not None:
-            per_kernel = {}
-            pk_bytes = (pmc or {}).get("per_kernel_hbm_bytes_per_step") if pmc and pmc.get("kernel_source_hash") == source_hash() else None
-            for i, nm in enumerate(("compact", "wide", "big", "huge")):
-                ms_k = (mode_t1[0][i] - mode_t0[0][i]) / args.steps
-                n_k = (mode_t1[1][i] - mode_t0[1][i]) / float(args.steps)
-                if n_k == 0:
-                    continue
-                b_k = pk_bytes.get(nm) if pk_bytes else None
-                per_kernel["lcb_process_kernel<%s>" % nm] = {
-                    "calls_per_step": n_k, "ms_per_step": ms_k, "avg_launch_ms": ms_k / n_k, "share_of_kernel_ms": ms_k / max(1e-9, kernel_ms / args.steps),
-                    "hbm_bytes_per_step": b_k, "achieved_gb_s": (b_k / (ms_k / 1000.0) / 1e9) if b_k and ms_k > 0 else None,
-                    "frac": (b_k / (ms_k / 1000.0) / 1e9 / HBM_PEAK_GBS) if b_k and ms_k > 0 else None}
         line = {
             "metric": "seed vertices/sec through BlocksFinder", "value": value, "unit": "seeds/s", "n_gpus": n_gpus, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -529,37 +503,130 @@ def main():
                        "host_ms_per_step": {"in_processor_incl_kernels": process_ms / args.steps, "dry_runs": plan_ms / args.steps,
                                             "commit_validation_other": ms_per_step - (process_ms + plan_ms) / args.steps},
                        "untimed_s": {"load_graph": t_load, "enumerate_seeds": t_seeds, "create_device_upload_tables": t_upload}},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "kernel": "lcb_process_kernel (all variants)", "launches_per_step": lps,
-                         "algorithmic_bytes_per_launch": abytes / max(1.0, lps), "avg_launch_ms": kernel_ms / max(1, launches),
-                         "algorithmic_bytes_per_step": abytes, "kernel_ms_per_step": kernel_busy_ms / args.steps, "bytes_per_seed": abytes / S,
-                         "kernel_ms_sum_over_streams_per_step": kernel_ms / args.steps, "kernel_ms_on_side_lanes_per_step": kernel_side_ms / args.steps,
-                         "event_counts_source": counts_src if not args.no_roofline else None,
-                         "per_kernel": per_kernel,
-                         "peak_measured_stream_triad": triad, "frac_of_measured_peak": achieved / triad if triad > 0 else None,
-                         "event_counts": ctr,
-                         "note": "latency-bound integer walk: a launch is as long as its longest seed; the event counts of the named workloads are the CPU oracle's at full size "
-                                 "(bench_event_counts.json; a stats-mode pass of the device reproduces them, n_compat_call / n_compat_step as upper bounds within 0.02%: "
-                                 "speculative results walk older bitmaps). achieved = algorithmic bytes / kernel_ms_per_step, and kernel_ms_per_step is the UNION of the "
-                                 "hipEvent-timed intervals of every process-kernel launch on every stream (the time the GPU was busy with them: the side-lane kernels run "
-                                 "beside the synchronous ones); kernel_ms_sum_over_streams_per_step is their plain sum - what a rocprofv3 --stats table of the same command sums to"},
         }
+        gff = None
+        if args.full:
+            # parity artefact of the timed run: GFF through the product's GenerateOutput
+            out_dir = os.path.join(w["dir"], "gpu_out")
+            finder.params = params
+            finder.GenerateOutput(out_dir, blocks=blocks, blocks_found=int(st["blocks_found"]))
+            gff = os.path.join(out_dir, "blocks_coords.gff")
+            # algorithmic bytes: one untimed pass of the engine in stats mode; the engine sums the event counters of exactly the
+            # Process() calls the reference makes (phase-start result of every seed + re-processing of every conflict)
+            ctr_file = os.path.join(w["dir"], "counters.json")
+            ctr = None
+            if gpus is not None and not args.no_roofline:
+                # the counting pass and the triad run on one device: a plain one beside the set (the counts do not depend on the GPU count)
+                dev = sibeliaz_amd.Device(storage, params, 0, **dev_opts)
+            if not args.no_roofline:
+                # the counts are a property of (input, parameters): the ones of the named workloads are kept in bench_event_counts.json
+                # (counted by `bench.py --full --recount` on the MI355X) so that a --full run need not repeat the 3-minute counting pass
+                known = json.load(open(os.path.join(ROOT, "bench_event_counts.json"))).get(args.workload) if os.path.exists(os.path.join(ROOT, "bench_event_counts.json")) else None
+                counts_src = None
+                # (--verify-counts counts them again when other sources than the ones of this build counted them)
+                if known and not args.recount and known["lcb_synth"] == w["synth"] and known["seeds"] == S and (known.get("source_hash") == source_hash() or not args.verify_counts):
+                    ctr = known["event_counts"]
+                    # the counts are a property of (input, parameters), pinned to the CPU oracle at full size; whether the sources of this build are the
+                    # ones that last re-counted them on the device is reported, not required
+                    counts_src = {"file": "bench_event_counts.json", "counted_by": known.get("source", ""), "source_hash_of_that_build": known.get("source_hash"),
+                                  "source_hash_of_this_build": source_hash(), "same_sources": known.get("source_hash") == source_hash()}
+                elif os.path.exists(ctr_file) and not args.recount:
+                    ctr = json.load(open(ctr_file))
+                else:
+                    t = time.time()
+                    dev.set_stats_mode(True)
+                    finder.FindBlocks(w["m"], w["b"], device=dev, seeds=seeds, count_events=1)
+                    dev.set_stats_mode(False)
+                    ctr = {k: int(finder.stats["ev_" + k]) for k in sibeliaz_amd.api.COUNTER_NAMES}
+                    json.dump(ctr, open(ctr_file, "w"))
+                    if args.write_counts:
+                        allc = json.load(open(os.path.join(ROOT, "bench_event_counts.json"))) if os.path.exists(os.path.join(ROOT, "bench_event_counts.json")) else {}
+                        allc[args.workload] = {"event_counts": ctr, "lcb_synth": w["synth"], "seeds": S, "workload": w["desc"], "source_hash": source_hash(),
+                                               "source": "stats-mode pass of the engine on the MI355X (bench.py --full --recount --write-counts); reference-semantics counts are a property of input + parameters"}
+                        json.dump(allc, open(os.path.join(ROOT, "bench_event_counts.json"), "w"), indent=1, sort_keys=True)
+                    dev.kernel_time()
+                    log("bench: stats-mode pass %.1fs: %s" % (time.time() - t, ctr))
+            abytes = algorithmic_bytes(ctr) if ctr else 0
+            kernel_s_per_step = kernel_busy_ms / 1000.0 / args.steps     # GPU time = the union of the kernels' intervals (never more than the step)
+            lps = launches / float(args.steps)
+            achieved = abytes / kernel_s_per_step / 1e9 if kernel_s_per_step > 0 else 0.0
+            triad = dev.hbm_triad() if dev is not None else 0.0
+            # HBM bytes per launch from the PMC counters: collected in separate rocprofv3 --pmc passes of this same command
+            # (scripts/gpu_r2_evidence.sh), committed with the profile summaries; only for the workload they were taken on
+            traffic, traffic_src, pmc = None, None, None
+            pmc_file = next((f for f in (os.path.join(ROOT, "profiles", r, "pmc_traffic.json") for r in ("r06", "r05")) if os.path.exists(f)), None)
+            if args.workload == "ecoli62" and n_gpus == 1 and pmc_file:
+                pmc = json.load(open(pmc_file))
+                traffic = pmc["hbm_bytes_per_launch"]
+                traffic_src = {"file": os.path.relpath(pmc_file, ROOT), "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (separate runs) of `bench.py --steps 1 --warmup 0` on this "
+                               "workload, FETCH_SIZE doubled (gfx950 correction of MI355X_MICROARCH.md), per process-kernel launch",
+                               "source_hash_of_that_build": pmc.get("kernel_source_hash"), "source_hash_of_this_build": source_hash(),
+                               "same_sources": pmc.get("kernel_source_hash") == source_hash()}
+            # per kernel variant: launches and hipEvent-timed kernel time of the timed region (all streams); HBM bytes from the PMC passes where they are of
+            # this build's sources (the reference-semantics event counts are per seed, not per variant: the algorithmic figure stays a whole-pass one)
+            per_kernel = None
+            if mode_t0 is not None and mode_t1 is not None:
+                per_kernel = {}
+                pk_bytes = (pmc or {}).get("per_kernel_hbm_bytes_per_step") if pmc and pmc.get("kernel_source_hash") == source_hash() else None
+                for i, nm in enumerate(("compact", "wide", "big", "huge")):
+                    ms_k = (mode_t1[0][i] - mode_t0[0][i]) / args.steps
+                    n_k = (mode_t1[1][i] - mode_t0[1][i]) / float(args.steps)
+                    if n_k == 0:
+                        continue
+                    b_k = pk_bytes.get(nm) if pk_bytes else None
+                    per_kernel["lcb_process_kernel<%s>" % nm] = {
+                        "calls_per_step": n_k, "ms_per_step": ms_k, "avg_launch_ms": ms_k / n_k, "share_of_kernel_ms": ms_k / max(1e-9, kernel_ms / args.steps),
+                        "hbm_bytes_per_step": b_k, "achieved_gb_s": (b_k / (ms_k / 1000.0) / 1e9) if b_k and ms_k > 0 else None,
+                        "frac": (b_k / (ms_k / 1000.0) / 1e9 / HBM_PEAK_GBS) if b_k and ms_k > 0 else None}
+            line["roofline"] = {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_source": traffic_src,
+                "kernel": "lcb_process_kernel (all variants)", "launches_per_step": lps,
+                "algorithmic_bytes_per_launch": abytes / max(1.0, lps), "avg_launch_ms": kernel_ms / max(1, launches),
+                "algorithmic_bytes_per_step": abytes, "kernel_ms_per_step": kernel_busy_ms / args.steps, "bytes_per_seed": abytes / S,
+                "kernel_ms_sum_over_streams_per_step": kernel_ms / args.steps, "kernel_ms_on_side_lanes_per_step": kernel_side_ms / args.steps,
+                "event_counts_source": counts_src if not args.no_roofline else None,
+                "per_kernel": per_kernel,
+                "peak_measured_stream_triad": triad, "frac_of_measured_peak": achieved / triad if triad > 0 else None,
+                "event_counts": ctr,
+                "note": "latency-bound integer walk: a launch is as long as its longest seed; the event counts of the named workloads are the CPU oracle's at full size "
+                        "(bench_event_counts.json; a stats-mode pass of the device reproduces them, n_compat_call / n_compat_step as upper bounds within 0.02%: "
+                        "speculative results walk older bitmaps). achieved = algorithmic bytes / kernel_ms_per_step, and kernel_ms_per_step is the UNION of the "
+                        "hipEvent-timed intervals of every process-kernel launch on every stream (the time the GPU was busy with them: the side-lane kernels run "
+                        "beside the synchronous ones); kernel_ms_sum_over_streams_per_step is their plain sum - what a rocprofv3 --stats table of the same command sums to"}
         if dev is not None:
             dev.close()
         if gpus is not None:
             gpus.close()
-        if n_gpus == 1 and not args.no_cli:
+        gpu_legs_ok = True       # (a GPU child cut off by its time limit: no further one is started)
+        if args.full and n_gpus == 1 and not args.no_cli:
             # metric part 2: wall-clock of the whole drop-in process to blocks_coords.gff
             cli_out = os.path.join(w["dir"], "cli_out")
+            left = deadline - time.time()
             t = time.time()
-            r = subprocess.run([os.path.join(BIN, "sibeliaz-lcb"), "--graph", w["graph"], w["fasta"], "-k", str(w["k"]), "-b", str(w["b"]), "-m", str(w["m"]),
-                                "-a", str(w["a"]), "-t", str(args.threads), "-o", cli_out, "--noseq"], capture_output=True, text=True)
-            line["wall_clock"] = {"sibeliaz_lcb_process_s": time.time() - t, "rc": r.returncode, "threads": args.threads,
-                                  "gff_md5_equal_to_timed_run": r.returncode == 0 and md5(os.path.join(cli_out, "blocks_coords.gff")) == md5(gff)}
-        if n_gpus == 1 and not args.no_cpu_baseline and args.workload in SAMPLES:
+            if left < 90.0:
+                line["wall_clock"] = {"skipped": "the budget of the --full run was spent"}
+            else:
+                try:
+                    r = subprocess.run([os.path.join(BIN, "sibeliaz-lcb"), "--graph", w["graph"], w["fasta"], "-k", str(w["k"]), "-b", str(w["b"]), "-m", str(w["m"]),
+                                        "-a", str(w["a"]), "-t", str(args.threads), "-o", cli_out, "--noseq"], capture_output=True, text=True, timeout=left)
+                    line["wall_clock"] = {"sibeliaz_lcb_process_s": time.time() - t, "rc": r.returncode, "threads": args.threads,
+                                          "gff_md5_equal_to_timed_run": r.returncode == 0 and md5(os.path.join(cli_out, "blocks_coords.gff")) == md5(gff)}
+                except subprocess.TimeoutExpired:
+                    line["wall_clock"] = {"timeout_s": left, "threads": args.threads}
+                    gpu_legs_ok = False
+        secondary = args.workload == "ecoli62" and n_gpus == 1 and not args.no_secondary and not args.secondary_leg and gpu_legs_ok
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and args.workload in SAMPLES:
+            # every leg of the protocol fits into what is left of the --full budget (the secondary shapes keep two minutes for themselves)
+            budget = min(args.cpu_baseline_budget, deadline - time.time() - (120.0 if secondary else 15.0))
             try:
-                cb = cpu_baseline_quick(args.workload, args.threads, gff) if args.secondary_leg else cpu_baseline(args.workload, args.threads, not args.sample_cpu_baseline, gff, args.cpu_baseline_budget)
+                if args.secondary_leg:
+                    cb = cpu_baseline_quick(args.workload, args.threads, gff, limit_s=max(10.0, min(120.0, budget)))
+                elif budget < 60.0:
+                    cb = None
+                    line["cpu_baseline_skipped"] = "the budget of the --full run was spent"
+                else:
+                    cb = cpu_baseline(args.workload, args.threads, not args.sample_cpu_baseline, gff, budget)
                 if cb:
                     line["cpu_baseline"] = cb
             except Exception as e:       # the reference's legs must never cost the line itself
@@ -567,8 +634,8 @@ def main():
         # the other shapes of BASELINE.json on the scoreboard. The k = 25 shapes (configs 4 / 5 at test size) are timed LIVE by this run, each with its own
         # roofline and a whole-workload reference leg ("measured_in_this_run": true). Entries of the round's evidence run (other workloads: a = 868, the
         # Gbp-scale shapes) are attached from profiles/ only if they were measured on a build of THESE sources, and say "measured_in_this_run": false.
-        if args.workload == "ecoli62" and n_gpus == 1 and not args.no_secondary and not args.secondary_leg:
-            sec = secondary_live(("primates8_test", "mice16_test"), args.threads, args.no_cpu_baseline)
+        if args.full and secondary:
+            sec = secondary_live(("primates8_test", "mice16_test"), args.threads, args.no_cpu_baseline, deadline)
             sec_file = os.path.join(ROOT, "profiles", "r06", "secondary.json")
             if os.path.exists(sec_file):
                 for e in json.load(open(sec_file)):

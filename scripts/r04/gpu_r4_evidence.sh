@@ -52,10 +52,10 @@ if len(tot) == 2:
 PY
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-LCB_VERBOSE=1 timeout 1200 python bench.py --steps 2 --warmup 1 > $O/bench_n1.json 2> $O/bench_n1.err
+LCB_VERBOSE=1 timeout 1200 python bench.py --full --steps 2 --warmup 1 > $O/bench_n1.json 2> $O/bench_n1.err
 tail -6 $O/bench_n1.err | cut -c1-400; cut -c1-1500 $O/bench_n1.json
 for w in primates8_test mice16_test; do
-  LCB_VERBOSE=1 timeout 600 python bench.py --workload $w --steps 3 --warmup 1 --cpu-baseline-budget 240 > $O/bench_n1_$w.json 2> $O/bench_n1_$w.err; cut -c1-400 $O/bench_n1_$w.json
+  LCB_VERBOSE=1 timeout 600 python bench.py --full --workload $w --steps 3 --warmup 1 --cpu-baseline-budget 240 > $O/bench_n1_$w.json 2> $O/bench_n1_$w.err; cut -c1-400 $O/bench_n1_$w.json
   python - <<PY
 import json
 d = json.load(open("$O/bench_n1_$w.json")); cb = d.get("cpu_baseline", {}); wc = d.get("wall_clock", {})

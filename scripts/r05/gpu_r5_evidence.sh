@@ -52,12 +52,12 @@ if len(tot) == 2:
 PY
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-LCB_VERBOSE=1 timeout 1100 python bench.py --steps 2 --warmup 1 --cpu-baseline-budget 330 > $O/bench_n1.json 2> $O/bench_n1.err
+LCB_VERBOSE=1 timeout 1100 python bench.py --full --steps 2 --warmup 1 --cpu-baseline-budget 330 > $O/bench_n1.json 2> $O/bench_n1.err
 grep "lcb engine" $O/bench_n1.err | tail -2 | cut -c1-400; cut -c1-1200 $O/bench_n1.json
 for w in primates8_test mice16_test; do
-  LCB_VERBOSE=1 timeout 500 python bench.py --workload $w --steps 3 --warmup 1 --cpu-baseline-budget 150 > $O/bench_n1_$w.json 2> $O/bench_n1_$w.err; cut -c1-300 $O/bench_n1_$w.json
+  LCB_VERBOSE=1 timeout 500 python bench.py --full --workload $w --steps 3 --warmup 1 --cpu-baseline-budget 150 > $O/bench_n1_$w.json 2> $O/bench_n1_$w.err; cut -c1-300 $O/bench_n1_$w.json
 done
-LCB_VERBOSE=1 timeout 400 python bench.py --workload ecoli62_a868 --steps 2 --warmup 1 --no-roofline > $O/bench_n1_ecoli62_a868.json 2> $O/bench_n1_ecoli62_a868.err; cut -c1-300 $O/bench_n1_ecoli62_a868.json
+LCB_VERBOSE=1 timeout 400 python bench.py --full --workload ecoli62_a868 --steps 2 --warmup 1 --no-roofline > $O/bench_n1_ecoli62_a868.json 2> $O/bench_n1_ecoli62_a868.err; cut -c1-300 $O/bench_n1_ecoli62_a868.json
 fi
 if [ "$MODE" = all ] || [ "$MODE" = big ]; then
 timeout 1500 python scripts/check_fullsize_scaled.py config4_primates8_4g_scaled > $O/fullsize_4g.log 2>&1; tail -4 $O/fullsize_4g.log

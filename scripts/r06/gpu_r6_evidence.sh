@@ -29,9 +29,9 @@ cd $R
 python scripts/r06/pmc_summary.py $O
 fi
 if has bench; then
-LCB_VERBOSE=1 timeout 1500 python bench.py --steps 3 --warmup 1 --cpu-baseline-budget 330 > $O/bench_n1.json 2> $O/bench_n1.err
+LCB_VERBOSE=1 timeout 1500 python bench.py --full --steps 3 --warmup 1 --cpu-baseline-budget 330 > $O/bench_n1.json 2> $O/bench_n1.err
 grep "lcb engine" $O/bench_n1.err | tail -2 | cut -c1-400; cut -c1-1500 $O/bench_n1.json
-LCB_VERBOSE=1 timeout 400 python bench.py --workload ecoli62_a868 --steps 2 --warmup 1 --no-roofline --no-secondary > $O/bench_n1_ecoli62_a868.json 2> $O/bench_n1_ecoli62_a868.err; cut -c1-300 $O/bench_n1_ecoli62_a868.json
+LCB_VERBOSE=1 timeout 400 python bench.py --full --workload ecoli62_a868 --steps 2 --warmup 1 --no-roofline --no-secondary > $O/bench_n1_ecoli62_a868.json 2> $O/bench_n1_ecoli62_a868.err; cut -c1-300 $O/bench_n1_ecoli62_a868.json
 fi
 big() {
   LCB_VERBOSE=1 LCB_TRACE_LAUNCHES=$O/trace_$1.tsv timeout $2 python scripts/check_fullsize_scaled.py $1 > $O/fullsize_$1.log 2>&1; grep -E "equal|FAILED|phase loop|lcb engine" $O/fullsize_$1.log | cut -c1-500

@@ -69,7 +69,7 @@ def _run_main(bench, monkeypatch, capsys, argv):
 def test_bench_line_fields(fake_gpu, monkeypatch, capsys):
     """One JSON line with the contract's fields, the roofline object from the committed-format event counts, the side-lane statistics."""
     bench = fake_gpu
-    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "2", "--warmup", "1", "--no-cli", "--no-cpu-baseline", "--no-roofline"])
+    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "2", "--warmup", "1", "--full", "--no-cli", "--no-cpu-baseline", "--no-roofline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in line
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["unit"] == "seeds/s" and line["config"]["workload"].startswith("10 synthetic strains")
@@ -82,13 +82,69 @@ def test_bench_line_fields(fake_gpu, monkeypatch, capsys):
     assert pk["lcb_process_kernel<wide>"]["avg_launch_ms"] == pytest.approx(6.0) and pk["lcb_process_kernel<wide>"]["hbm_bytes_per_step"] is None
     assert "secondary" not in line                      # (only the headline workload carries the other shapes)
     # with the roofline: the counting pass (a workload without committed counts), the triad, the traffic note
-    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "1", "--warmup", "0", "--no-cli", "--no-cpu-baseline"])
+    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "1", "--warmup", "0", "--full", "--no-cli", "--no-cpu-baseline"])
     assert set(line["roofline"]["event_counts"]) == set(__import__("sibeliaz_amd").api.COUNTER_NAMES) and line["roofline"]["peak_measured_stream_triad"] == 4700.0
     assert line["roofline"]["bound"] == "hbm" and line["roofline"]["peak"] == 8000.0 and "frac" in line["roofline"]
 
 
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(fake_gpu, monkeypatch, capsys, tmp_path):
+    """A plain run (no --full) times --steps passes and prints the headline line, and nothing of --full runs: no counting pass or triad, no
+    whole-process run, no reference legs, no secondary shapes. --dump-outputs writes the last step's block list and counts as float64."""
+    import sibeliaz_amd
+    bench = fake_gpu
+    calls = []
+
+    def find_blocks(self, m, b, device=None, seeds=None, comm=None, threads=1, **engine):
+        calls.append(1)
+        _fake_find_blocks(self, m, b, device=device, seeds=seeds, comm=comm, threads=threads, **engine)
+        self.blocks = np.array([(1, 0, 10, 200), (-1, 3, 5000000000, 5000000300), (2, 1, 7, 90)], dtype=sibeliaz_amd.BLOCK_DTYPE)
+        self.stats.update(blocks_found=2, failures=len(calls))
+        return self.blocks
+
+    def refuse(what):
+        def f(*a, **k):
+            raise AssertionError("a plain run ran " + what)
+        return f
+    monkeypatch.setattr(sibeliaz_amd.BlocksFinder, "FindBlocks", find_blocks)
+    monkeypatch.setattr(sibeliaz_amd.BlocksFinder, "GenerateOutput", refuse("GenerateOutput"))
+    for name in ("cpu_baseline", "cpu_baseline_quick", "secondary_live", "run_reference"):
+        monkeypatch.setattr(bench, name, refuse(name))
+    monkeypatch.setattr(_FakeDevice, "hbm_triad", refuse("the triad"))
+    monkeypatch.setattr(_FakeDevice, "set_stats_mode", refuse("the counting pass"))
+    monkeypatch.setattr(bench.subprocess, "run", refuse("a child process"))
+    out = tmp_path / "dump"
+    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "3", "--warmup", "2", "--dump-outputs", str(out)])
+    assert len(calls) == 5 and line["steps"] == 3 and line["warmup"] == 2 and line["n_gpus"] == 1
+    assert line["metric"] == "seed vertices/sec through BlocksFinder" and line["unit"] == "seeds/s" and line["higher_is_better"] is True and line["dtype"] == "int32"
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(line["config"]["seeds"] / (line["ms_per_step"] / 1000.0))
+    assert not {"roofline", "wall_clock", "cpu_baseline", "cpu_baseline_error", "cpu_baseline_skipped", "secondary"} & set(line)
+    assert sorted(os.listdir(out)) == ["blocks.npy", "counts.npy"]
+    b, c = np.load(out / "blocks.npy"), np.load(out / "counts.npy")
+    assert b.dtype == np.float64 and b.tolist() == [[1, 0, 10, 200], [-1, 3, 5000000000, 5000000300], [2, 1, 7, 90]]
+    assert c.dtype == np.float64 and c.tolist() == [2, 5]          # (the conflict count of the fifth call: the last timed step's)
+
+
+def test_dumped_block_list_beyond_the_cap_is_a_fixed_sample(monkeypatch, tmp_path):
+    import sibeliaz_amd
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 640)
+    blocks = np.zeros(100, dtype=sibeliaz_amd.BLOCK_DTYPE)
+    blocks["id"], blocks["start"] = np.arange(100), np.arange(100) * 7
+    stats = {"blocks_found": 100, "failures": 0}
+    bench.dump_outputs(str(tmp_path / "a"), blocks, stats)
+    bench.dump_outputs(str(tmp_path / "b"), blocks, stats)
+    for fn in ("blocks.npy", "blocks_rows.npy", "counts.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / fn), np.load(tmp_path / "b" / fn))
+    rows, b = np.load(tmp_path / "a" / "blocks_rows.npy"), np.load(tmp_path / "a" / "blocks.npy")
+    assert b.shape == (10, 4) and b.nbytes + rows.nbytes <= 640 and list(b[:, 0]) == list(rows) and list(b[:, 2]) == list(rows * 7)
+
+
 def test_reference_legs_are_bounded_and_never_cost_the_line(fake_gpu, monkeypatch, capsys):
     bench = fake_gpu
+    if not os.path.exists(bench.REF_EXE):
+        # oracle/_ref is built only where the reference's sources are: the oracle's CLI stands in for it (the reference restated, with its
+        # command line, banners and GFF - tests/test_edge_cases.py), so that the protocol's plumbing is checked everywhere
+        monkeypatch.setattr(bench, "REF_EXE", os.path.join(ROOT, "oracle", "lcb_oracle"))
     w = bench.ensure_workload("ecoli10_tiny")
     # a run that exceeds its limit is killed and reported as such
     assert bench.run_reference(w, 1, "limit", 0.2) == "timeout"
@@ -101,7 +157,7 @@ def test_reference_legs_are_bounded_and_never_cost_the_line(fake_gpu, monkeypatc
     assert cb["kind"] == "reference" and cb["gff_md5_equal"] is True and cb["value"] > 0 and any(k.endswith("_whole") for k in cb["legs"])
     # a leg that raises does not cost the line
     monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: (_ for _ in ()).throw(RuntimeError("boom")))
-    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "1", "--warmup", "0", "--no-cli", "--no-roofline"])
+    line = _run_main(bench, monkeypatch, capsys, ["--workload", "ecoli10_tiny", "--steps", "1", "--warmup", "0", "--full", "--no-cli", "--no-roofline"])
     assert "cpu_baseline" not in line and "boom" in line["cpu_baseline_error"]
 
 
@@ -175,7 +231,7 @@ def test_secondary_entries_are_timed_by_child_runs_and_condensed(fake_gpu, monke
         return R("noise\n" + json.dumps(child) + "\n")
     monkeypatch.setattr(bench.subprocess, "run", fake_run)
     sec = bench.secondary_live(("primates8_test", "mice16_test"), 4)
-    assert all("--secondary-leg" in c and "--no-cli" in c for c in seen) and len(seen) == 2
+    assert all("--secondary-leg" in c and "--no-cli" in c and "--full" in c for c in seen) and len(seen) == 2
     assert sec[0]["measured_in_this_run"] is True and sec[0]["speedup_over_cpu_baseline"] == pytest.approx(2.5) and sec[0]["roofline"]["frac"] == 0.0011
     assert sec[0]["sources"] == bench.source_hash() and sec[0]["cpu_baseline"]["gff_md5_equal"] is True
     assert sec[1]["workload"] == "mice16_test" and "error" in sec[1]
