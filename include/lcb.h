@@ -131,6 +131,36 @@ const uint64_t* lcb_graph_chr_start(const lcb_graph* g);        /* [n_chr+1] */
 const int32_t* lcb_graph_pos_id(const lcb_graph* g);            /* [n_pos] Position::id,  junctionstorage.h:142 */
 const uint32_t* lcb_graph_pos_pos(const lcb_graph* g);          /* [n_pos] Position::pos, junctionstorage.h:143 */
 
+/* ---- junction finder: twopaco's role (reference call site sibeliaz:145; format common/junctionapi.h:80-136) on one MI355X.
+ * Writes the junction file that lcb_graph_load reads, byte-identical to what `lcb-mkgraph` (the CPU tool) writes for the same
+ * input: canonical k-mers, k odd in 3..31, a k-mer is a junction iff it has >= 2 distinct successor or predecessor characters
+ * over both strands of the whole input or an occurrence touches a sequence end or a non-ACGT neighbour; ids are 1-based ranks
+ * in order of first appearance among junction occurrences in file order. The k-mer table and the sequence live in HBM
+ * (DESIGN.md §10 has the layout and the memory formula); an input that does not fit fails before anything is allocated.
+ * These structs are allocated by the caller and carry the LCB_ABI_VERSION they were compiled against. */
+typedef struct {            /* 0 = default; the output never depends on these (tests sweep them) */
+    uint32_t abi;           /* = LCB_ABI_VERSION */
+    uint32_t table_log2;    /* INITIAL k-mer table capacity, log2 slots; default by the input as in lcb-mkgraph: max(2^20, next power
+                               of two >= windows / 2). A table that fills beyond 0.9 is doubled and the insertion starts over */
+    uint32_t tile_windows;  /* windows per classify/emit tile; default 2^22, at most 2^30 */
+    uint32_t reserved;
+} lcb_junction_opts;
+typedef struct {
+    int64_t records;        /* sequences of the input (= separator records written) */
+    int64_t windows;        /* sum over the sequences of max(0, length - k + 1) */
+    int64_t occurrences;    /* junction occurrences written */
+    int64_t junction_kmers; /* distinct junction k-mers (= largest id) */
+    int64_t table_slots;    /* final capacity of the k-mer table */
+    int64_t table_rebuilds; /* times the table was found too full and the insertion started over with twice the slots */
+    int64_t tiles;          /* classify/emit tiles */
+    double read_ms, upload_ms, insert_ms, emit_ms, write_ms;   /* host wall time of read (FASTA + encoding) and write (records + file; overlaps
+                                                                  the device); device phases hipEvent-timed */
+} lcb_junction_stats;
+/* No CPU fallback: without a GPU this fails (the CPU way to the same bytes is the lcb-mkgraph tool). On any failure no out_file
+ * (and no partial file) is left behind. opts and stats may be NULL. */
+int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int device_ordinal,
+                        const lcb_junction_opts* opts, const char* out_file, lcb_junction_stats* stats);
+
 /* ---- seeds: bundle enumeration + std::sort (blocksfinder.h:461-503,517). *out is malloc'ed; free with lcb_free. */
 int64_t lcb_enumerate_seeds(const lcb_graph* g, int threads, lcb_seed** out);
 void lcb_free(void* p);

@@ -78,6 +78,20 @@ class DeviceOpts(C.Structure):
         self.abi = ABI_VERSION
 
 
+class JunctionOpts(C.Structure):
+    """lcb_junction_opts: tuning knobs of the GPU junction finder, 0 = default; the output never depends on them."""
+    _fields_ = [(n, C.c_uint32) for n in ("abi", "table_log2", "tile_windows", "reserved")]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.abi = ABI_VERSION
+
+
+class JunctionStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("records", "windows", "occurrences", "junction_kmers", "table_slots", "table_rebuilds", "tiles")] + [
+        (n, C.c_double) for n in ("read_ms", "upload_ms", "insert_ms", "emit_ms", "write_ms")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in COUNTER_NAMES]
 
@@ -97,6 +111,7 @@ EXPORTS = [
     "lcb_committer_free", "lcb_committer_commit_phase", "lcb_committer_take_marks", "lcb_committer_n_blocks", "lcb_committer_blocks",
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
+    "lcb_junctions_build",
 ]
 
 
@@ -130,6 +145,7 @@ def load_library():
     L.lcb_graph_pos_id.argtypes = [vp]
     L.lcb_graph_pos_pos.restype = vp
     L.lcb_graph_pos_pos.argtypes = [vp]
+    L.lcb_junctions_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.POINTER(JunctionOpts), C.c_char_p, C.POINTER(JunctionStats)]
     L.lcb_enumerate_seeds.restype = i64
     L.lcb_enumerate_seeds.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.lcb_free.argtypes = [vp]
@@ -194,6 +210,25 @@ def _np_from(ptr, n, dtype):
         return np.zeros(0, dtype=dtype)
     buf = (C.c_char * (n * dtype.itemsize)).from_address(ptr)
     return np.frombuffer(buf, dtype=dtype, count=n).copy()
+
+
+def build_junctions(fasta_files, k, out_file, device=0, **opts):
+    """twopaco's role on one MI355X (lcb_junctions_build): FASTA files -> the junction file JunctionStorage reads, byte-identical to
+    what the CPU tool `lcb-mkgraph` writes. opts: fields of lcb_junction_opts (table_log2, tile_windows). -> the stats as a dict."""
+    L = load_library()
+    if isinstance(fasta_files, (str, bytes, os.PathLike)):
+        fasta_files = [fasta_files]
+    o = JunctionOpts()
+    for name, v in opts.items():
+        if name not in ("abi", "table_log2", "tile_windows"):
+            raise TypeError("unknown junction option %r" % name)
+        setattr(o, name, int(v))
+    files = [os.fsencode(f) for f in fasta_files]
+    arr = (C.c_char_p * max(1, len(files)))(*files)
+    st = JunctionStats()
+    if L.lcb_junctions_build(arr, len(files), int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(st)):
+        raise _err(L)
+    return {f: getattr(st, f) for f, _ in JunctionStats._fields_}
 
 
 class JunctionStorage:

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """In-tree build driver (no cmake needed): `python sibeliaz_amd/build.py [tools|lib|cli|oracle|all]`.
 
-  tools   g++    -> sibeliaz_amd/bin/lcb-synth, lcb-mkgraph      (input generators)
-  lib     hipcc  -> sibeliaz_amd/libsibeliaz_amd.so              (HIP kernels + C-ABI, gfx950)
+  tools   g++    -> sibeliaz_amd/bin/lcb-synth, lcb-mkgraph      (input generators; `lcb-mkgraph --gpu N` loads the library
+                                                                  at run time and runs its junction finder instead)
+  lib     hipcc  -> sibeliaz_amd/libsibeliaz_amd.so              (HIP kernels + C-ABI, gfx950: block finder, junction finder)
   cli     hipcc  -> sibeliaz_amd/bin/sibeliaz-lcb                (drop-in executable)
   oracle  gcc    -> oracle/liblcb_oracle.so, oracle/lcb_oracle   (test infrastructure)
           + oracle/_ref when /root/reference exists (build container only)
@@ -21,8 +22,8 @@ BIN = os.path.join(PKG, "bin")
 LIB = os.path.join(PKG, "libsibeliaz_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-LIB_SRC = ["graph.cpp", "bundles.cpp", "commit.cpp", "engine.cpp", "output.cpp", "capi.cpp", "comm.hip", "device.hip"]
-LIB_HDR = ["lcb_host.h", "lcb_kernel.h", "lcb_device.h", "lcb_segments.h", "lcb_kernel_limits.h"]
+LIB_SRC = ["graph.cpp", "bundles.cpp", "commit.cpp", "engine.cpp", "output.cpp", "capi.cpp", "comm.hip", "device.hip", "junctions.hip"]
+LIB_HDR = ["lcb_host.h", "lcb_kernel.h", "lcb_device.h", "lcb_segments.h", "lcb_kernel_limits.h", "lcb_fasta.h", "lcb_junction_kernels.h"]
 
 
 def _newer(srcs, out):
@@ -42,8 +43,8 @@ def build_tools():
     for name, src in (("lcb-synth", "synth.cpp"), ("lcb-mkgraph", "mkgraph.cpp")):
         s = os.path.join(CSRC, "tools", src)
         o = os.path.join(BIN, name)
-        if _newer([s], o):
-            _run(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", o, s])
+        if _newer([s, os.path.join(CSRC, "lcb_fasta.h"), os.path.join(ROOT, "include", "lcb.h")], o):
+            _run(["g++", "-O2", "-std=c++17", "-fopenmp", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", o, s, "-ldl"])
 
 
 def hip_flags():

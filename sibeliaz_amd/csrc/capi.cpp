@@ -1,5 +1,6 @@
 // capi.cpp — the extern "C" surface declared in include/lcb.h: argument checks, exception -> return
 // code translation, thread-local error text. No logic lives here.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -77,6 +78,31 @@ const char* lcb_graph_chr_name(const lcb_graph* g, int64_t chr) { return g->chrN
 const uint64_t* lcb_graph_chr_start(const lcb_graph* g) { return g->chrStart.data(); }
 const int32_t* lcb_graph_pos_id(const lcb_graph* g) { return g->posId.data(); }
 const uint32_t* lcb_graph_pos_pos(const lcb_graph* g) { return g->posPos.data(); }
+
+int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int device_ordinal, const lcb_junction_opts* opts,
+                        const char* out_file, lcb_junction_stats* stats)
+{
+    LCB_TRY
+    // everything that can be refused without a device is refused before the device is touched
+    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError("lcb_junctions_build: k must be odd and in 3..31, not " + std::to_string(k));
+    if (!fasta_files || n_fasta < 1) throw LcbError("lcb_junctions_build: no FASTA file");
+    if (!out_file || !*out_file) throw LcbError("lcb_junctions_build: no output file");
+    if (opts && opts->abi != (uint32_t)LCB_ABI_VERSION)
+        throw LcbError("lcb_junction_opts.abi is " + std::to_string(opts->abi) + ", this library has LCB_ABI_VERSION " + std::to_string(LCB_ABI_VERSION));
+    if (opts && opts->table_log2 > 40) throw LcbError("lcb_junction_opts.table_log2 is " + std::to_string(opts->table_log2) + ": at most 40");
+    if (opts && opts->tile_windows > (1u << 30)) throw LcbError("lcb_junction_opts.tile_windows is " + std::to_string(opts->tile_windows) + ": at most 2^30");
+    std::vector<std::string> fa;
+    for (int i = 0; i < n_fasta; i++) {
+        if (!fasta_files[i]) throw LcbError("lcb_junctions_build: FASTA path " + std::to_string(i) + " is null");
+        FILE* f = fopen(fasta_files[i], "rb");
+        if (!f) throw LcbError(std::string("lcb_junctions_build: cannot open ") + fasta_files[i]);
+        fclose(f);
+        fa.push_back(fasta_files[i]);
+    }
+    lcb_junctions_build_impl(fa, k, device_ordinal, opts, out_file, stats);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
 
 int64_t lcb_enumerate_seeds(const lcb_graph* g, int threads, lcb_seed** out)
 {

@@ -38,6 +38,9 @@ void lcb_set_error(const std::string& msg);
 
 // graph.cpp
 lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::string>& fasta, int k, int abundance, int threads);
+// junctions.hip — GPU junction finder (byte-identical to tools/mkgraph.cpp); arguments are already validated
+void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts* opts, const std::string& outFile,
+                              lcb_junction_stats* stats);
 // bundles.cpp
 void lcb_enumerate_seeds_impl(const lcb_graph& g, int threads, std::vector<lcb_seed>& out);
 // output.cpp

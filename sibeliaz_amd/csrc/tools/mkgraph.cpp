@@ -12,6 +12,9 @@
 // sequence end / a non-ACGT character. id = 1-based rank of the canonical k-mer in order of first
 // appearance among junctions; the sign is + iff the occurrence spells the canonical form.
 // The k-mer table is filled by all cores (OpenMP, lock-free open addressing); the output does not depend on the thread count.
+//
+// --gpu <ordinal>: the same bytes from the GPU junction finder of libsibeliaz_amd.so (csrc/junctions.hip, lcb_junctions_build), loaded
+// at run time so that this tool stays a plain g++ build. Nothing falls back: a missing library or GPU is an error.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +28,12 @@
 #include <memory>
 #include <chrono>
 
+#include <dlfcn.h>
+#include <unistd.h>
+
+#include "lcb.h"
+#include "lcb_fasta.h"
+
 namespace {
 
 double nowS() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -32,36 +41,9 @@ const bool kVerbose = getenv("LCB_MKGRAPH_VERBOSE") != nullptr;
 #define PHASE(name) do { if (kVerbose) { const double t_ = nowS(); fprintf(stderr, "lcb-mkgraph: %-28s %.2f s\n", name, t_ - tPhase); tPhase = t_; } } while (0)
 
 
-struct Record { std::string name; std::string seq; };
-
-void readFasta(const std::string& file, std::vector<Record>& out) {
-    FILE* f = fopen(file.c_str(), "rb");
-    if (!f) throw std::runtime_error("cannot open " + file);
-    std::vector<char> buf(1 << 20);
-    bool inHeader = false;
-    std::string header;
-    size_t n;
-    while ((n = fread(buf.data(), 1, buf.size(), f)) > 0) {
-        for (size_t i = 0; i < n; i++) {
-            char c = buf[i];
-            if (inHeader) {
-                if (c == '\n') {
-                    inHeader = false;
-                    size_t e = 0;
-                    while (e < header.size() && !isspace((unsigned char)header[e])) e++;
-                    out.push_back({header.substr(0, e), std::string()});
-                } else header.push_back(c);
-            } else if (c == '>') { inHeader = true; header.clear(); }
-            else if (!isspace((unsigned char)c) && !out.empty()) out.back().seq.push_back((char)toupper((unsigned char)c));
-        }
-    }
-    fclose(f);
-}
-
-inline int code(char c) {
-    switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; }
-    return -1;
-}
+using lcb_fasta::Record;
+using lcb_fasta::readFasta;
+using lcb_fasta::code;
 
 // Open-addressing map canonical k-mer -> {succ mask(4) | pred mask(4) << 4 | forced << 8}, junction id. Fixed capacity,
 // filled concurrently: a slot is claimed with a compare-and-swap on its key, the masks are OR-ed in atomically.
@@ -138,22 +120,71 @@ void forEachKmer(const std::string& seq, int k, size_t from, size_t to, F fn) {
     }
 }
 
+// --gpu: $LCB_LIB, or libsibeliaz_amd.so next to the bin/ directory of this executable.
+int runOnGpu(const std::vector<std::string>& fasta, int k, int ordinal, unsigned tableLog2, unsigned tileWindows, const std::string& out)
+{
+    try {
+        std::string lib;
+        if (const char* e = getenv("LCB_LIB")) lib = e;
+        else {
+            char self[4096];
+            const ssize_t n = readlink("/proc/self/exe", self, sizeof(self) - 1);
+            if (n <= 0) throw std::runtime_error("cannot locate the executable to find libsibeliaz_amd.so (set LCB_LIB)");
+            lib.assign(self, (size_t)n);
+            lib = lib.substr(0, lib.rfind('/')) + "/../libsibeliaz_amd.so";
+        }
+        void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!h) { const char* why = dlerror(); throw std::runtime_error("--gpu: cannot load " + lib + ": " + (why ? why : "unknown reason")); }
+        typedef int (*build_fn)(const char* const*, int, int, int, const lcb_junction_opts*, const char*, lcb_junction_stats*);
+        typedef const char* (*error_fn)(void);
+        const build_fn build = (build_fn)dlsym(h, "lcb_junctions_build");
+        const error_fn lastError = (error_fn)dlsym(h, "lcb_last_error");
+        if (!build || !lastError) throw std::runtime_error("--gpu: " + lib + " has no lcb_junctions_build (an older library?)");
+        std::vector<const char*> files;
+        for (const std::string& f : fasta) files.push_back(f.c_str());
+        lcb_junction_opts o;
+        memset(&o, 0, sizeof(o));
+        o.abi = LCB_ABI_VERSION; o.table_log2 = tableLog2; o.tile_windows = tileWindows;
+        lcb_junction_stats st;
+        memset(&st, 0, sizeof(st));
+        if (build(files.data(), (int)files.size(), k, ordinal, &o, out.c_str(), &st) != LCB_OK) throw std::runtime_error(lastError());
+        if (kVerbose) {
+            const std::pair<const char*, double> phases[] = {{"read FASTA", st.read_ms}, {"upload (GPU)", st.upload_ms}, {"k-mer table (GPU)", st.insert_ms},
+                                                             {"junction occurrences (GPU)", st.emit_ms}, {"records (host, overlapped)", st.write_ms}};
+            for (const auto& p : phases) fprintf(stderr, "lcb-mkgraph: %-28s %.2f s\n", p.first, p.second / 1000.0);
+            fprintf(stderr, "lcb-mkgraph: gpu: insert %.3f ms, emit %.3f ms, upload %.3f ms; %lld windows, table 2^%d slots after %lld rebuilds, %lld tiles\n", st.insert_ms,
+                    st.emit_ms, st.upload_ms, (long long)st.windows, __builtin_ctzll((unsigned long long)st.table_slots), (long long)st.table_rebuilds, (long long)st.tiles);
+        }
+        fprintf(stderr, "lcb-mkgraph: %zu records, %llu junction occurrences, %u junction k-mers\n", (size_t)st.records, (unsigned long long)st.occurrences,
+                (unsigned)st.junction_kmers);
+    } catch (std::exception& e) {
+        fprintf(stderr, "lcb-mkgraph: error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-    int k = 25;
+    int k = 25, gpu = -1;
+    unsigned tableLog2 = 0, tileWindows = 0;
     std::string out;
     std::vector<std::string> fasta;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) k = atoi(argv[++i]);
         else if (a == "-o" && i + 1 < argc) out = argv[++i];
+        else if (a == "--gpu" && i + 1 < argc) gpu = atoi(argv[++i]);
+        else if (a == "--table-log2" && i + 1 < argc) tableLog2 = (unsigned)atoi(argv[++i]);
+        else if (a == "--tile-windows" && i + 1 < argc) tileWindows = (unsigned)atoi(argv[++i]);
         else fasta.push_back(a);
     }
     if (out.empty() || fasta.empty() || k < 3 || k > 31 || k % 2 == 0) {
-        fprintf(stderr, "usage: lcb-mkgraph -k <odd 3..31> -o junctions.bin <fasta...>\n");
+        fprintf(stderr, "usage: lcb-mkgraph -k <odd 3..31> -o junctions.bin [--gpu <ordinal> [--table-log2 N] [--tile-windows N]] <fasta...>\n");
         return 2;
     }
+    if (gpu >= 0) return runOnGpu(fasta, k, gpu, tableLog2, tileWindows, out);
     try {
         double tPhase = nowS();
         std::vector<Record> rec;
