@@ -161,6 +161,40 @@ typedef struct {
 int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int device_ordinal,
                         const lcb_junction_opts* opts, const char* out_file, lcb_junction_stats* stats);
 
+/* ---- the same file from a k-mer table built in PARTITIONS of the canonical k-mer space, one after the other (twopaco's --rounds):
+ * for inputs whose whole table does not fit the device. A bitmap of junction windows (one bit per base) is all that survives a
+ * partition; ids come from a second table that holds the junction k-mers only. The bytes do not depend on the number of
+ * partitions (DESIGN.md §10 has the argument and the memory formula). One partition = lcb_junctions_build's single-table path. */
+typedef struct {
+    uint32_t abi;           /* = LCB_ABI_VERSION */
+    uint32_t table_log2;    /* INITIAL capacity of EACH partition's table, log2 slots; default max(2^20, next power of two >=
+                               windows / (2 * partitions)). A partition whose table fills beyond 0.9 starts over with twice the slots */
+    uint32_t tile_windows;  /* as in lcb_junction_opts */
+    uint32_t partitions;    /* 0 = the smallest number whose phase-A peak fits the budget (lcb_junctions_plan), 1..64 = fixed */
+    uint64_t mem_budget;    /* bytes of device memory the build may use; 0 = what hipMemGetInfo reports free (which also caps a non-zero budget) */
+    uint32_t reserved[4];   /* zero */
+} lcb_junction_opts_ex;
+typedef struct {
+    lcb_junction_stats base;        /* table_slots: the largest partition table; table_rebuilds: over all tables; insert_ms: all partitions;
+                                       emit_ms: filling the junction table + the tiles */
+    int64_t partitions;             /* as planned or given */
+    int64_t junction_windows;       /* bits set in the bitmap (= base.occurrences) */
+    int64_t junction_table_slots;   /* final capacity of the table of junction k-mers; 0 with one partition (there is none) */
+    uint64_t peak_device_bytes;     /* most device memory held at one time, by the build's own account */
+    double mark_ms;                 /* device time of the marking passes */
+    int64_t passes;                 /* insert + mark passes completed: partitions, plus one for every time a partition whose doubled table
+                                       would not fit the budget was split in two instead */
+} lcb_junction_stats_ex;
+int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, int device_ordinal,
+                           const lcb_junction_opts_ex* opts, const char* out_file, lcb_junction_stats_ex* stats);
+/* "Will my input fit, and in how many passes": pure arithmetic, no device, the function the build itself calls. windows and
+ * seq_bytes as in the stats (seq_bytes = bases + sequences + 1: one byte per base, one breaker around every sequence). With
+ * opts->partitions == 0: the smallest P in 1..64 whose phase-A peak  seq_bytes + 8 * ceil(seq_bytes / 64) + 12 * S_P + 64  fits
+ * `budget`, and that peak; an error that names both numbers if 64 partitions do not fit. With a fixed P: that P's peak (budget is
+ * not looked at). opts may be NULL (= automatic, defaults). */
+int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget,
+                       int32_t* partitions, uint64_t* need_bytes);
+
 /* ---- seeds: bundle enumeration + std::sort (blocksfinder.h:461-503,517). *out is malloc'ed; free with lcb_free. */
 int64_t lcb_enumerate_seeds(const lcb_graph* g, int threads, lcb_seed** out);
 void lcb_free(void* p);

@@ -92,6 +92,20 @@ class JunctionStats(C.Structure):
         (n, C.c_double) for n in ("read_ms", "upload_ms", "insert_ms", "emit_ms", "write_ms")]
 
 
+class JunctionOptsEx(C.Structure):
+    """lcb_junction_opts_ex: lcb_junction_opts plus the number of partitions (0 = automatic) and the device-memory budget."""
+    _fields_ = [(n, C.c_uint32) for n in ("abi", "table_log2", "tile_windows", "partitions")] + [("mem_budget", C.c_uint64), ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.abi = ABI_VERSION
+
+
+class JunctionStatsEx(C.Structure):
+    _fields_ = [("base", JunctionStats), ("partitions", C.c_int64), ("junction_windows", C.c_int64), ("junction_table_slots", C.c_int64),
+                ("peak_device_bytes", C.c_uint64), ("mark_ms", C.c_double), ("passes", C.c_int64)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in COUNTER_NAMES]
 
@@ -111,7 +125,7 @@ EXPORTS = [
     "lcb_committer_free", "lcb_committer_commit_phase", "lcb_committer_take_marks", "lcb_committer_n_blocks", "lcb_committer_blocks",
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
-    "lcb_junctions_build",
+    "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan",
 ]
 
 
@@ -146,6 +160,8 @@ def load_library():
     L.lcb_graph_pos_pos.restype = vp
     L.lcb_graph_pos_pos.argtypes = [vp]
     L.lcb_junctions_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.POINTER(JunctionOpts), C.c_char_p, C.POINTER(JunctionStats)]
+    L.lcb_junctions_build_ex.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.POINTER(JunctionOptsEx), C.c_char_p, C.POINTER(JunctionStatsEx)]
+    L.lcb_junctions_plan.argtypes = [i64, i64, C.POINTER(JunctionOptsEx), C.c_uint64, C.POINTER(C.c_int32), u64p]
     L.lcb_enumerate_seeds.restype = i64
     L.lcb_enumerate_seeds.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.lcb_free.argtypes = [vp]
@@ -212,23 +228,50 @@ def _np_from(ptr, n, dtype):
     return np.frombuffer(buf, dtype=dtype, count=n).copy()
 
 
-def build_junctions(fasta_files, k, out_file, device=0, **opts):
+def _junction_opts(cls, opts, allowed):
+    o = cls()
+    for name, v in opts.items():
+        if name not in allowed:
+            raise TypeError("unknown junction option %r" % name)
+        setattr(o, name, int(v))
+    return o
+
+
+def build_junctions(fasta_files, k, out_file, device=0, partitions=None, mem_budget=None, **opts):
     """twopaco's role on one MI355X (lcb_junctions_build): FASTA files -> the junction file JunctionStorage reads, byte-identical to
-    what the CPU tool `lcb-mkgraph` writes. opts: fields of lcb_junction_opts (table_log2, tile_windows). -> the stats as a dict."""
+    what the CPU tool `lcb-mkgraph` writes. opts: fields of lcb_junction_opts (table_log2, tile_windows). -> the stats as a dict.
+    partitions (1..64, or 0 = as many as the budget asks for) and mem_budget (bytes of device memory, 0 = what is free) go through
+    lcb_junctions_build_ex: the k-mer table is built in that many passes, the bytes stay the same, the dict gains the extended stats."""
     L = load_library()
     if isinstance(fasta_files, (str, bytes, os.PathLike)):
         fasta_files = [fasta_files]
-    o = JunctionOpts()
-    for name, v in opts.items():
-        if name not in ("abi", "table_log2", "tile_windows"):
-            raise TypeError("unknown junction option %r" % name)
-        setattr(o, name, int(v))
     files = [os.fsencode(f) for f in fasta_files]
     arr = (C.c_char_p * max(1, len(files)))(*files)
-    st = JunctionStats()
-    if L.lcb_junctions_build(arr, len(files), int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(st)):
+    if partitions is None and mem_budget is None:
+        o = _junction_opts(JunctionOpts, opts, ("abi", "table_log2", "tile_windows"))
+        st = JunctionStats()
+        if L.lcb_junctions_build(arr, len(files), int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(st)):
+            raise _err(L)
+        return {f: getattr(st, f) for f, _ in JunctionStats._fields_}
+    o = _junction_opts(JunctionOptsEx, dict(opts, partitions=partitions or 0, mem_budget=mem_budget or 0), ("abi", "table_log2", "tile_windows", "partitions", "mem_budget"))
+    sx = JunctionStatsEx()
+    if L.lcb_junctions_build_ex(arr, len(files), int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(sx)):
         raise _err(L)
-    return {f: getattr(st, f) for f, _ in JunctionStats._fields_}
+    out = {f: getattr(sx.base, f) for f, _ in JunctionStats._fields_}
+    out.update({f: getattr(sx, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
+    return out
+
+
+def plan_junctions(windows, seq_bytes, budget, **opts):
+    """lcb_junctions_plan: will an input of that many k-mer windows and sequence bytes (bases + sequences + 1) fit `budget` bytes of
+    device memory, and in how many partitions? No device is needed. opts: table_log2, partitions (0 or absent = the smallest that fits,
+    an LcbError if 64 do not; 1..64 = the need of exactly that many). -> (partitions, need_bytes)."""
+    L = load_library()
+    o = _junction_opts(JunctionOptsEx, opts, ("abi", "table_log2", "tile_windows", "partitions"))
+    p, need = C.c_int32(0), C.c_uint64(0)
+    if L.lcb_junctions_plan(int(windows), int(seq_bytes), C.byref(o), int(budget), C.byref(p), C.byref(need)):
+        raise _err(L)
+    return int(p.value), int(need.value)
 
 
 class JunctionStorage:

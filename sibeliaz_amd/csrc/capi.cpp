@@ -104,6 +104,48 @@ int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int 
     LCB_CATCH(LCB_ERR)
 }
 
+namespace {
+void checkJunctionOptsEx(const lcb_junction_opts_ex* opts)
+{
+    if (!opts) return;
+    if (opts->abi != (uint32_t)LCB_ABI_VERSION)
+        throw LcbError("lcb_junction_opts_ex.abi is " + std::to_string(opts->abi) + ", this library has LCB_ABI_VERSION " + std::to_string(LCB_ABI_VERSION));
+    if (opts->partitions > 64) throw LcbError("lcb_junction_opts_ex.partitions is " + std::to_string(opts->partitions) + ": at most 64 (0 = automatic)");
+    if (opts->table_log2 > 40) throw LcbError("lcb_junction_opts_ex.table_log2 is " + std::to_string(opts->table_log2) + ": at most 40");
+    if (opts->tile_windows > (1u << 30)) throw LcbError("lcb_junction_opts_ex.tile_windows is " + std::to_string(opts->tile_windows) + ": at most 2^30");
+}
+}  // namespace
+
+int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, int device_ordinal, const lcb_junction_opts_ex* opts,
+                           const char* out_file, lcb_junction_stats_ex* stats)
+{
+    LCB_TRY
+    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError("lcb_junctions_build_ex: k must be odd and in 3..31, not " + std::to_string(k));
+    if (!fasta_files || n_fasta < 1) throw LcbError("lcb_junctions_build_ex: no FASTA file");
+    if (!out_file || !*out_file) throw LcbError("lcb_junctions_build_ex: no output file");
+    checkJunctionOptsEx(opts);
+    std::vector<std::string> fa;
+    for (int i = 0; i < n_fasta; i++) {
+        if (!fasta_files[i]) throw LcbError("lcb_junctions_build_ex: FASTA path " + std::to_string(i) + " is null");
+        FILE* f = fopen(fasta_files[i], "rb");
+        if (!f) throw LcbError(std::string("lcb_junctions_build_ex: cannot open ") + fasta_files[i]);
+        fclose(f);
+        fa.push_back(fasta_files[i]);
+    }
+    lcb_junctions_build_ex_impl(fa, k, device_ordinal, opts, out_file, stats);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
+
+int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget, int32_t* partitions, uint64_t* need_bytes)
+{
+    LCB_TRY
+    checkJunctionOptsEx(opts);
+    lcb_junctions_plan_impl(windows, seq_bytes, opts, budget, partitions, need_bytes);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
+
 int64_t lcb_enumerate_seeds(const lcb_graph* g, int threads, lcb_seed** out)
 {
     LCB_TRY

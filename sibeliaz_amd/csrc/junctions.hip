@@ -11,6 +11,9 @@
 //              slot's value word to PENDING | (2^30 - 1 - its index in the tile) with an atomicMax: the maximum is the first
 //              occurrence, whatever the arrival order. A scan over the first occurrences gives the ids, a scan over the junction
 //              windows the places of the records.
+//   partitions the table can be built in P passes over the input, one part of the canonical k-mer space per pass (jPartition), when
+//              the whole table does not fit: a pass leaves one bit per window in a bitmap, the ids then come from a table of the
+//              junction k-mers alone, through the same tile pipeline. One partition = the single-table path above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,18 +53,20 @@ struct Run {
     uint8_t* dCodes = nullptr;
     unsigned long long* dKey = nullptr;
     uint32_t* dVal = nullptr;
+    unsigned long long* dBitmap = nullptr;
     unsigned long long* dWslot = nullptr;
     JRecord* dOut = nullptr;
     uint32_t *dCntJ = nullptr, *dCntF = nullptr;
-    JState* dState = nullptr;
-    JState* hState = nullptr;
+    JState* dState = nullptr;       // LCB_JUNCTION_STATE_BYTES: the JState, and behind it the count of marked windows
+    JState* hState = nullptr;       // (pinned, the same block)
     JRecord* hOut[2] = {nullptr, nullptr};
     FILE* f = nullptr;
     std::string part;
+    uint64_t budget = 0, live = 0, peak = 0;     // the run's own account of its device memory
     ~Run()
     {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : {(void*)dCodes, (void*)dKey, (void*)dVal, (void*)dWslot, (void*)dOut, (void*)dCntJ, (void*)dCntF, (void*)dState})
+        for (void* p : {(void*)dCodes, (void*)dKey, (void*)dVal, (void*)dBitmap, (void*)dWslot, (void*)dOut, (void*)dCntJ, (void*)dCntF, (void*)dState})
             if (p) (void)hipFree(p);
         if (hState) (void)hipHostFree(hState);
         for (JRecord* p : hOut) if (p) (void)hipHostFree(p);
@@ -70,19 +75,47 @@ struct Run {
         if (f) fclose(f);
         if (!part.empty()) remove(part.c_str());
     }
+    // Would `bytes` more fit? Against the budget by the run's own account, and against what the device reports free.
+    bool fits(uint64_t bytes) const
+    {
+        size_t freeB = 0, totalB = 0;
+        return live + bytes <= budget && hipMemGetInfo(&freeB, &totalB) == hipSuccess && bytes <= (uint64_t)freeB;
+    }
+    template <class T>
+    void alloc(T*& p, uint64_t bytes, const char* what)
+    {
+        size_t freeB = 0, totalB = 0;
+        HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+        if (live + bytes > budget || bytes > (uint64_t)freeB)
+            throw LcbError(std::string("lcb_junctions_build: ") + what + " needs " + std::to_string(bytes) + " bytes of device memory on top of the " + std::to_string(live) +
+                           " in use: the budget is " + std::to_string(budget) + ", " + std::to_string((uint64_t)freeB) + " are free");
+        HIP_CHECK(hipMalloc((void**)&p, bytes));
+        live += bytes;
+        peak = std::max(peak, live);
+    }
+    template <class T>
+    void release(T*& p, uint64_t bytes)
+    {
+        if (!p) return;
+        HIP_CHECK(hipFree(p));
+        p = nullptr;
+        live -= bytes;
+    }
 };
 
-}  // namespace
+static_assert(sizeof(JState) + sizeof(unsigned long long) <= LCB_JUNCTION_STATE_BYTES, "the state block holds the JState and the count of marked windows");
 
-void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts* opts, const std::string& outFile,
-                              lcb_junction_stats* stats)
+// P == 1: the single-table path. P == 0: as many partitions as lcb_junctions_plan finds for the budget. Otherwise P partitions.
+void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t tableLog2, uint32_t tileWindowsOpt, uint32_t P, uint64_t budgetOpt,
+           const std::string& outFile, lcb_junction_stats_ex* stats)
 {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         throw LcbError("no HIP device available: lcb_junctions_build runs only on the GPU (there is no CPU fallback; the CPU tool is lcb-mkgraph)");
     if (ordinal < 0 || ordinal >= count) throw LcbError("HIP device ordinal out of range");
-    lcb_junction_stats S;
-    memset(&S, 0, sizeof(S));
+    lcb_junction_stats_ex X;
+    memset(&X, 0, sizeof(X));
+    lcb_junction_stats& S = X.base;
 
     // ---- read + encode (in place: the sequence strings become the code bytes)
     double t = nowMs();
@@ -108,43 +141,54 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     S.windows = (int64_t)nWindows;
     S.read_ms = nowMs() - t;
 
-    // ---- sizes, and whether they fit, before anything is allocated
-    const uint32_t tileWindows = opts && opts->tile_windows ? opts->tile_windows : (1u << 22);
+    // ---- the budget, the number of partitions, and whether the first phase fits, before anything is allocated
+    Run R;
+    HIP_CHECK(hipSetDevice(ordinal));
+    size_t freeB = 0, totalB = 0;
+    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+    R.budget = budgetOpt ? std::min<uint64_t>(budgetOpt, freeB) : (uint64_t)freeB;
+    const uint32_t tileWindows = tileWindowsOpt ? tileWindowsOpt : (1u << 22);
     const uint32_t tileBuf = (uint32_t)std::min<uint64_t>(tileWindows, len);
     const uint32_t nbMax = gridFor(tileBuf, JT);
-    uint32_t capLog2 = 20;
-    if (opts && opts->table_log2) capLog2 = opts->table_log2;
-    else while ((1ull << capLog2) < nWindows / 2) capLog2++;
-    const uint64_t fixedBytes = len + (uint64_t)tileBuf * (sizeof(unsigned long long) + sizeof(JRecord)) + (uint64_t)nbMax * 8 + sizeof(JState);
-    auto tableBytes = [](uint32_t log2) { return (1ull << log2) * (sizeof(unsigned long long) + sizeof(uint32_t)); };
-    HIP_CHECK(hipSetDevice(ordinal));
-    auto needFits = [&](uint64_t need, const char* what) {
-        size_t freeB = 0, totalB = 0;
-        HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-        if (need > (uint64_t)freeB)
-            throw LcbError(std::string("lcb_junctions_build: ") + what + " needs " + std::to_string(need) + " bytes of device memory, " + std::to_string((uint64_t)freeB) +
-                           " are free (sequence " + std::to_string(len) + " + 12 bytes per table slot + 24 bytes per tile window)");
-    };
-    needFits(fixedBytes + tableBytes(capLog2), "the input");
+    const uint64_t tileBytes = (uint64_t)tileBuf * (sizeof(unsigned long long) + sizeof(JRecord)) + (uint64_t)nbMax * 8;
+    const uint64_t bitmapWords = (len + 63) / 64;
+    if (P == 0) {
+        lcb_junction_opts_ex o;
+        memset(&o, 0, sizeof(o));
+        o.table_log2 = tableLog2;
+        int32_t planned = 0;
+        lcb_junctions_plan_impl((int64_t)nWindows, (int64_t)len, &o, R.budget, &planned, nullptr);
+        P = (uint32_t)planned;
+    }
+    uint32_t capLog2 = tableLog2 ? tableLog2 : lcb_junction_default_log2(nWindows, P);
+    const uint64_t need = P == 1 ? len + tileBytes + LCB_JUNCTION_STATE_BYTES + lcb_junction_table_bytes(capLog2) : lcb_junction_phase_a_bytes(nWindows, len, tableLog2, P);
+    if (need > R.budget)
+        throw LcbError("lcb_junctions_build: the input needs " + std::to_string(need) + " bytes of device memory with " + std::to_string(P) + " partition(s), " +
+                       std::to_string(R.budget) + " may be used (sequence " + std::to_string(len) + " + 12 bytes per table slot + " +
+                       (P == 1 ? "24 bytes per tile window)" : "one bit per base)"));
+    X.partitions = P;
 
-    Run R;
     HIP_CHECK(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
     HIP_CHECK(hipEventCreate(&R.evA));
     HIP_CHECK(hipEventCreate(&R.evB));
     HIP_CHECK(hipEventCreate(&R.evCopy[0]));
     HIP_CHECK(hipEventCreate(&R.evCopy[1]));
-    HIP_CHECK(hipMalloc((void**)&R.dCodes, len));
-    HIP_CHECK(hipMalloc((void**)&R.dWslot, (size_t)tileBuf * sizeof(unsigned long long)));
-    HIP_CHECK(hipMalloc((void**)&R.dOut, (size_t)tileBuf * sizeof(JRecord)));
-    HIP_CHECK(hipMalloc((void**)&R.dCntJ, (size_t)nbMax * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc((void**)&R.dCntF, (size_t)nbMax * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc((void**)&R.dState, sizeof(JState)));
-    HIP_CHECK(hipHostMalloc((void**)&R.hState, sizeof(JState), hipHostMallocDefault));
+    R.alloc(R.dCodes, len, "the sequence");
+    R.alloc(R.dState, LCB_JUNCTION_STATE_BYTES, "the state");
+    auto allocTiles = [&]() {
+        R.alloc(R.dWslot, (uint64_t)tileBuf * sizeof(unsigned long long), "the tile buffers");
+        R.alloc(R.dOut, (uint64_t)tileBuf * sizeof(JRecord), "the tile buffers");
+        R.alloc(R.dCntJ, (uint64_t)nbMax * sizeof(uint32_t), "the tile buffers");
+        R.alloc(R.dCntF, (uint64_t)nbMax * sizeof(uint32_t), "the tile buffers");
+    };
+    if (P == 1) allocTiles();
+    HIP_CHECK(hipHostMalloc((void**)&R.hState, LCB_JUNCTION_STATE_BYTES, hipHostMallocDefault));
     float ms = 0;
 
     // ---- upload
     HIP_CHECK(hipEventRecord(R.evA, R.stream));
     HIP_CHECK(hipMemsetAsync(R.dCodes, 4, len, R.stream));
+    HIP_CHECK(hipMemsetAsync(R.dState, 0, LCB_JUNCTION_STATE_BYTES, R.stream));
     HIP_CHECK(hipStreamSynchronize(R.stream));
     for (size_t r = 0; r < rec.size(); r++)
         if (!rec[r].seq.empty()) HIP_CHECK(hipMemcpy(R.dCodes + base[r], rec[r].seq.data(), rec[r].seq.size(), hipMemcpyHostToDevice));
@@ -156,32 +200,101 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     for (size_t r = 0; r < rec.size(); r++) recLen[r] = rec[r].seq.size();
     std::vector<lcb_fasta::Record>().swap(rec);      // (the host copy of the sequence is no longer needed)
 
-    // ---- the k-mer table: insert everything; too full -> twice the slots, from the start
+    // One attempt to fill a fresh table of 2^log2 slots with `insert` (a launch on R.stream); false: too full, the table is freed again.
     uint64_t mask = 0;
-    for (;; capLog2++) {
-        if (capLog2 > 40) throw LcbError("lcb_junctions_build: the k-mer table would need more than 2^40 slots");
-        if (R.dKey) { HIP_CHECK(hipFree(R.dKey)); R.dKey = nullptr; }
-        if (R.dVal) { HIP_CHECK(hipFree(R.dVal)); R.dVal = nullptr; }
-        needFits(tableBytes(capLog2), "the k-mer table");
-        const uint64_t cap = 1ull << capLog2;
+    auto tryTable = [&](uint32_t log2, const char* what, double& phaseMs, auto insert) {
+        const uint64_t cap = 1ull << log2;
         mask = cap - 1;
-        HIP_CHECK(hipMalloc((void**)&R.dKey, cap * sizeof(unsigned long long)));
-        HIP_CHECK(hipMalloc((void**)&R.dVal, cap * sizeof(uint32_t)));
+        R.alloc(R.dKey, cap * sizeof(unsigned long long), what);
+        R.alloc(R.dVal, cap * sizeof(uint32_t), what);
         HIP_CHECK(hipEventRecord(R.evA, R.stream));
         HIP_CHECK(hipMemsetAsync(R.dKey, 0, cap * sizeof(unsigned long long), R.stream));
         HIP_CHECK(hipMemsetAsync(R.dVal, 0, cap * sizeof(uint32_t), R.stream));
         HIP_CHECK(hipMemsetAsync(R.dState, 0, sizeof(JState), R.stream));
-        junctionInsert<<<gridFor(len, J_WPB), JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, R.dState);
+        insert();
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(R.evB, R.stream));
-        HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, sizeof(JState), hipMemcpyDeviceToHost, R.stream));
+        HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, R.stream));
         HIP_CHECK(hipStreamSynchronize(R.stream));
-        HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
-        S.insert_ms += ms;
-        if (!R.hState->full && R.hState->used * 10 <= cap * 9) break;
+        float e = 0;
+        HIP_CHECK(hipEventElapsedTime(&e, R.evA, R.evB));
+        phaseMs += e;
+        if (!R.hState->full && R.hState->used * 10 <= cap * 9) return true;
         S.table_rebuilds++;
+        R.release(R.dKey, cap * sizeof(unsigned long long));
+        R.release(R.dVal, cap * sizeof(uint32_t));
+        return false;
+    };
+    auto freeTable = [&]() {
+        R.release(R.dKey, (mask + 1) * sizeof(unsigned long long));
+        R.release(R.dVal, (mask + 1) * sizeof(uint32_t));
+    };
+    const uint32_t gridAll = gridFor(len, J_WPB);
+    unsigned long long* const dMarked = (unsigned long long*)((char*)R.dState + sizeof(JState));
+
+    if (P == 1) {
+        // ---- the k-mer table: insert everything; too full -> twice the slots, from the start
+        for (;; capLog2++) {
+            if (capLog2 > 40) throw LcbError("lcb_junctions_build: the k-mer table would need more than 2^40 slots");
+            if (tryTable(capLog2, "the k-mer table", S.insert_ms,
+                         [&]() { junctionInsert<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, R.dState); }))
+                break;
+        }
+        S.table_slots = (int64_t)(mask + 1);
+        X.passes = 1;
+    } else {
+        // ---- phase A: partition after partition, insert + mark. (M, r) = the k-mers with jPartition(kmer, M) == r. A table too full is
+        // doubled; where the doubled table would not fit the budget, the partition is split instead: (M, r) = (2M, r) + (2M, r + M).
+        R.alloc(R.dBitmap, bitmapWords * 8, "the bitmap of junction windows");
+        HIP_CHECK(hipMemsetAsync(R.dBitmap, 0, bitmapWords * 8, R.stream));
+        struct Part { uint32_t M, r, log2; };
+        std::vector<Part> todo;
+        for (uint32_t p = P; p-- > 0;) todo.push_back(Part{P, p, capLog2});
+        while (!todo.empty()) {
+            Part q = todo.back();
+            todo.pop_back();
+            bool split = false;
+            while (!tryTable(q.log2, "the k-mer table of a partition", S.insert_ms, [&]() {
+                junctionInsertPart<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, R.dState, q.M, q.r);
+            })) {
+                if (q.log2 < 40 && R.fits(lcb_junction_table_bytes(q.log2 + 1))) { q.log2++; continue; }
+                if (2 * q.M > (uint32_t)J_MAX_PARTS)
+                    throw LcbError("lcb_junctions_build: the k-mer table of partition " + std::to_string(q.r) + " of " + std::to_string(q.M) + " is too full at 2^" +
+                                   std::to_string(q.log2) + " slots, and twice the slots (" + std::to_string(lcb_junction_table_bytes(q.log2 + 1)) + " bytes on top of " +
+                                   std::to_string(R.live) + " in use) do not fit the budget of " + std::to_string(R.budget));
+                todo.push_back(Part{2 * q.M, q.r + q.M, q.log2});
+                todo.push_back(Part{2 * q.M, q.r, q.log2});
+                split = true;
+                break;
+            }
+            if (split) continue;
+            S.table_slots = std::max<int64_t>(S.table_slots, (int64_t)(mask + 1));
+            HIP_CHECK(hipEventRecord(R.evA, R.stream));
+            junctionMarkPart<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, q.M, q.r, R.dBitmap, dMarked, R.dState);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventRecord(R.evB, R.stream));
+            HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, R.stream));
+            HIP_CHECK(hipStreamSynchronize(R.stream));
+            HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
+            X.mark_ms += ms;
+            if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a k-mer of the input is missing from the table of its partition");
+            freeTable();
+            X.passes++;
+        }
+        // ---- phase B: the table of the junction k-mers (every key of it is a junction), then the tiles as with one table
+        const uint64_t nJ = *(const unsigned long long*)((const char*)R.hState + sizeof(JState));
+        X.junction_windows = (int64_t)nJ;
+        allocTiles();
+        uint32_t jLog2 = lcb_junction_default_log2(nJ, 1);
+        for (;; jLog2++) {
+            if (jLog2 > 40) throw LcbError("lcb_junctions_build: the table of junction k-mers would need more than 2^40 slots");
+            if (tryTable(jLog2, "the table of junction k-mers (phase B is not partitioned)", S.emit_ms,
+                         [&]() { junctionFillMarked<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, R.dState); }))
+                break;
+        }
+        if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a marked position holds no window");
+        X.junction_table_slots = (int64_t)(mask + 1);
     }
-    S.table_slots = (int64_t)(mask + 1);
 
     // ---- classify + emit, tile by tile in file order; the host turns tile t - 1 into records while the device works on tile t
     HIP_CHECK(hipHostMalloc((void**)&R.hOut[0], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
@@ -218,14 +331,15 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
         const uint32_t tileLen = (uint32_t)std::min<uint64_t>(tileWindows, len - t0);
         const uint32_t nb = gridFor(tileLen, JT);
         HIP_CHECK(hipEventRecord(R.evA, R.stream));
-        junctionClassify<<<gridFor(tileLen, J_WPB), JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
+        if (P == 1) junctionClassify<<<gridFor(tileLen, J_WPB), JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
+        else junctionClassifyMarked<<<gridFor(tileLen, J_WPB), JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
         junctionMarkFirst<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, R.dCntF);
         junctionScan<<<1, 1024, 0, R.stream>>>(R.dCntJ, R.dCntF, nb, R.dState);
         junctionAssignIds<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntF, R.dState);
         junctionEmit<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, t0, R.dOut);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(R.evB, R.stream));
-        HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, sizeof(JState), hipMemcpyDeviceToHost, R.stream));
+        HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, R.stream));
         if (tile > 0) drain((int)((tile - 1) & 1), prevN);
         HIP_CHECK(hipStreamSynchronize(R.stream));
         HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
@@ -240,6 +354,8 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
         S.occurrences += (int64_t)prevN;
     }
     if (tile > 0) drain((int)((tile - 1) & 1), prevN);
+    if (P == 1) X.junction_windows = S.occurrences;
+    else if (S.occurrences != X.junction_windows) throw LcbError("lcb_junctions_build: internal error: the tiles found another number of junction windows than the passes marked");
     const double tw = nowMs();
     for (; curRec < recLen.size(); curRec++) put(0xFFFFFFFFu, INT64_MAX);
     flushBuf();
@@ -251,5 +367,22 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     S.write_ms += nowMs() - tw;
     S.junction_kmers = (int64_t)ids;
     S.tiles = tile;
-    if (stats) *stats = S;
+    X.peak_device_bytes = R.peak;
+    if (stats) *stats = X;
+}
+
+}  // namespace
+
+void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts* opts, const std::string& outFile,
+                              lcb_junction_stats* stats)
+{
+    lcb_junction_stats_ex X;
+    build(fasta, k, ordinal, opts ? opts->table_log2 : 0, opts ? opts->tile_windows : 0, 1, 0, outFile, &X);
+    if (stats) *stats = X.base;
+}
+
+void lcb_junctions_build_ex_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex* opts, const std::string& outFile,
+                                 lcb_junction_stats_ex* stats)
+{
+    build(fasta, k, ordinal, opts ? opts->table_log2 : 0, opts ? opts->tile_windows : 0, opts ? opts->partitions : 0, opts ? opts->mem_budget : 0, outFile, stats);
 }

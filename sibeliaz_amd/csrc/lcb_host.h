@@ -41,6 +41,14 @@ lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::
 // junctions.hip — GPU junction finder (byte-identical to tools/mkgraph.cpp); arguments are already validated
 void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts* opts, const std::string& outFile,
                               lcb_junction_stats* stats);
+void lcb_junctions_build_ex_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex* opts, const std::string& outFile,
+                                 lcb_junction_stats_ex* stats);
+// junction_plan.cpp — the memory arithmetic of the partitioned build (no device): what lcb_junctions_plan answers and junctions.hip obeys
+constexpr uint64_t LCB_JUNCTION_STATE_BYTES = 64;      // the device-side state block (JState + the count of marked windows)
+uint64_t lcb_junction_table_bytes(uint32_t log2);      // 12 bytes per slot
+uint32_t lcb_junction_default_log2(uint64_t windows, uint32_t partitions);
+uint64_t lcb_junction_phase_a_bytes(uint64_t windows, uint64_t seqBytes, uint32_t tableLog2, uint32_t partitions);   // tableLog2 0 = default
+void lcb_junctions_plan_impl(int64_t windows, int64_t seqBytes, const lcb_junction_opts_ex* opts, uint64_t budget, int32_t* partitions, uint64_t* need);
 // bundles.cpp
 void lcb_enumerate_seeds_impl(const lcb_graph& g, int threads, std::vector<lcb_seed>& out);
 // output.cpp

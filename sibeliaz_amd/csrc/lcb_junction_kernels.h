@@ -31,10 +31,18 @@ struct JState {
 
 struct JRecord { unsigned long long g; long long id; };
 
-__device__ __forceinline__ uint64_t jMix(uint64_t x)
+__host__ __device__ __forceinline__ uint64_t jMix(uint64_t x)
 {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
     return x;
+}
+
+// The partition of a canonical k-mer when the table is built in P passes (1..J_MAX_PARTS), one part of the k-mer space per pass: bits
+// 40..63 of the hash. A slot index uses bits below 40 (mask < 2^40), so the k-mers of one partition still spread over all its slots.
+constexpr int J_MAX_PARTS = 64;
+__host__ __device__ __forceinline__ uint32_t jPartition(uint64_t kmer, uint32_t P)
+{
+    return (uint32_t)(jMix(kmer) >> 40) % P;
 }
 
 __device__ __forceinline__ bool jIsJunction(uint32_t v)
@@ -251,6 +259,188 @@ __global__ __launch_bounds__(JT) void junctionEmit(const unsigned long long* __r
     if (j) {
         const long long id = (long long)(val[w & W_SLOT] & 0x7FFFFFFFu);
         out[offJ[blockIdx.x] + rank] = JRecord{t0 + i, (w & W_FWD) ? id : -id};
+    }
+}
+
+// ---- the partitioned build (DESIGN.md §10 "Partitioned passes"): the table of pass p holds the k-mers with jPartition(kmer, P) == p only.
+// All occurrences of a k-mer, on both strands, share the canonical form and so the pass: its masks are complete there. What survives a
+// pass is one bit per position of the code array (bit g = window g is a junction occurrence); ids come from a second table that
+// holds the junction k-mers alone.
+
+// junctionInsert restricted to the windows of partition p.
+__global__ __launch_bounds__(JT) void junctionInsertPart(const uint8_t* __restrict__ codes, uint64_t len, int k, unsigned long long* key, uint32_t* val,
+                                                         uint64_t mask, JState* st, uint32_t P, uint32_t p)
+{
+    __shared__ uint8_t s[J_WPB + 40];
+    __shared__ uint32_t claimed;
+    const uint64_t b0 = (uint64_t)blockIdx.x * J_WPB;
+    if (threadIdx.x == 0) claimed = 0;
+    jLoadCodes(s, codes, len, b0, k);
+    __syncthreads();
+    uint32_t mine = 0;
+    bool stop = __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    for (int j = 0; j < J_RUN && !stop; j++) {
+        const int w = j * JT + threadIdx.x;
+        if (b0 + (uint64_t)w >= len) break;
+        uint64_t kmer; bool isFwd; uint32_t bits;
+        if (!jWindow(s + w, k, kmer, isFwd, bits)) continue;
+        if (jPartition(kmer, P) != p) continue;
+        const unsigned long long want = kmer + 1;
+        uint64_t h = jMix(kmer) & mask;
+        bool done = false;
+        for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
+            unsigned long long cur = key[h];
+            if (cur == 0) {
+                cur = atomicCAS(&key[h], 0ull, want);
+                if (cur == 0) { mine++; cur = want; }
+            }
+            if (cur == want) {
+                if ((val[h] & bits) != bits) atomicOr(&val[h], bits);
+                done = true;
+                break;
+            }
+            if ((probes & 255) == 255 && __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        }
+        if (!done) { atomicOr(&st->full, 1u); stop = true; }
+    }
+    if (mine) atomicAdd(&claimed, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && claimed) {
+        const unsigned long long u = atomicAdd(&st->used, (unsigned long long)claimed) + claimed;
+        if (u * 10 > (mask + 1) * 9) atomicOr(&st->full, 1u);
+    }
+}
+
+// After a complete insertion of partition p: bit g of bitmap[] for every window g of the partition whose k-mer is a junction. Window
+// w = j * 256 + lane of a workgroup whose base is a multiple of 2048: the 64 lanes of a wavefront hold, in every iteration, exactly the
+// 64 windows of ONE aligned bitmap word, and no other wavefront of the launch has a window of that word. So one lane ORs the ballot in
+// with a plain read-modify-write: no atomic, and no bit depends on an arrival order (the passes are launches behind each other on
+// one stream). *marked += the bits set; a partition is marked once, so the sum over the passes is the number of junction windows.
+__global__ __launch_bounds__(JT) void junctionMarkPart(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ key,
+                                                       const uint32_t* __restrict__ val, uint64_t mask, uint32_t P, uint32_t p, unsigned long long* bitmap,
+                                                       unsigned long long* marked, JState* st)
+{
+    __shared__ uint8_t s[J_WPB + 40];
+    __shared__ uint32_t found;
+    const uint64_t b0 = (uint64_t)blockIdx.x * J_WPB;
+    if (threadIdx.x == 0) found = 0;
+    jLoadCodes(s, codes, len, b0, k);
+    __syncthreads();
+    uint32_t mine = 0;
+    for (int j = 0; j < J_RUN; j++) {               // (no lane leaves the loop early: every lane of a wavefront reaches the ballot)
+        const int w = j * JT + threadIdx.x;
+        const uint64_t g = b0 + (uint64_t)w;
+        bool junction = false;
+        uint64_t kmer; bool isFwd; uint32_t bits;
+        if (g < len && jWindow(s + w, k, kmer, isFwd, bits) && jPartition(kmer, P) == p) {
+            const unsigned long long want = kmer + 1;
+            uint64_t h = jMix(kmer) & mask;
+            bool hit = false;
+            for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
+                const unsigned long long cur = key[h];
+                if (cur == want) { hit = true; break; }
+                if (cur == 0) break;
+            }
+            if (!hit) atomicOr(&st->lost, 1u);
+            else junction = jIsJunction(val[h]);
+        }
+        const unsigned long long b = __ballot(junction);
+        if (b != 0 && (threadIdx.x & 63) == 0) {    // (b != 0: a window of this word lies inside the array, so the word exists)
+            bitmap[g >> 6] |= b;
+            mine += (uint32_t)__popcll(b);
+        }
+    }
+    if (mine) atomicAdd(&found, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && found) atomicAdd(marked, (unsigned long long)found);
+}
+
+// The junction table: the k-mer of every window with a bit, with 0x100 | the window's bits - jIsJunction holds for every key of it.
+// The same probing and the same `full` protocol as junctionInsert.
+__global__ __launch_bounds__(JT) void junctionFillMarked(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ bitmap,
+                                                         unsigned long long* key, uint32_t* val, uint64_t mask, JState* st)
+{
+    __shared__ uint8_t s[J_WPB + 40];
+    __shared__ uint32_t claimed;
+    const uint64_t b0 = (uint64_t)blockIdx.x * J_WPB;
+    if (threadIdx.x == 0) claimed = 0;
+    jLoadCodes(s, codes, len, b0, k);
+    __syncthreads();
+    uint32_t mine = 0;
+    bool stop = __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    for (int j = 0; j < J_RUN && !stop; j++) {
+        const int w = j * JT + threadIdx.x;
+        const uint64_t g = b0 + (uint64_t)w;
+        if (g >= len) break;
+        if (!((bitmap[g >> 6] >> (g & 63)) & 1ull)) continue;
+        uint64_t kmer; bool isFwd; uint32_t bits;
+        if (!jWindow(s + w, k, kmer, isFwd, bits)) { atomicOr(&st->lost, 1u); continue; }     // (a bit without a window: cannot happen)
+        bits |= 0x100u;
+        const unsigned long long want = kmer + 1;
+        uint64_t h = jMix(kmer) & mask;
+        bool done = false;
+        for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
+            unsigned long long cur = key[h];
+            if (cur == 0) {
+                cur = atomicCAS(&key[h], 0ull, want);
+                if (cur == 0) { mine++; cur = want; }
+            }
+            if (cur == want) {
+                if ((val[h] & bits) != bits) atomicOr(&val[h], bits);
+                done = true;
+                break;
+            }
+            if ((probes & 255) == 255 && __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        }
+        if (!done) { atomicOr(&st->full, 1u); stop = true; }
+    }
+    if (mine) atomicAdd(&claimed, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && claimed) {
+        const unsigned long long u = atomicAdd(&st->used, (unsigned long long)claimed) + claimed;
+        if (u * 10 > (mask + 1) * 9) atomicOr(&st->full, 1u);
+    }
+}
+
+// junctionClassify in front of the junction table: a window without a bit is W_NONE without a probe; a window with one is looked up
+// and casts the first-occurrence vote. The rest of the tile pipeline (junctionMarkFirst .. junctionEmit) runs unchanged behind it.
+__global__ __launch_bounds__(JT) void junctionClassifyMarked(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ bitmap,
+                                                             const unsigned long long* __restrict__ key, uint32_t* val, uint64_t mask, uint64_t t0, uint32_t tileLen,
+                                                             unsigned long long* wslot, JState* st)
+{
+    __shared__ uint8_t s[J_WPB + 40];
+    const uint32_t i0 = blockIdx.x * (uint32_t)J_WPB;
+    jLoadCodes(s, codes, len, t0 + i0, k);
+    __syncthreads();
+    for (int j = 0; j < J_RUN; j++) {
+        const int w = j * JT + threadIdx.x;
+        const uint32_t i = i0 + (uint32_t)w;
+        if (i >= tileLen) break;
+        const uint64_t g = t0 + i;
+        unsigned long long out = W_NONE;
+        uint64_t kmer; bool isFwd; uint32_t bits;
+        if ((bitmap[g >> 6] >> (g & 63)) & 1ull) {
+            bool found = false;
+            uint64_t h = 0;
+            if (jWindow(s + w, k, kmer, isFwd, bits)) {
+                const unsigned long long want = kmer + 1;
+                h = jMix(kmer) & mask;
+                for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
+                    const unsigned long long cur = key[h];
+                    if (cur == want) { found = true; break; }
+                    if (cur == 0) break;
+                }
+            }
+            if (!found) atomicOr(&st->lost, 1u);
+            else {
+                const uint32_t v = val[h], vote = V_PEND | (V_IDX - i);
+                if (v & V_ID) {}
+                else if (v & V_PEND) { if (v < vote) atomicMax(&val[h], vote); }
+                else atomicMax(&val[h], vote);      // (every key of this table is a junction: its value carries 0x100)
+                out = h | (isFwd ? W_FWD : 0ull);
+            }
+        }
+        wslot[i] = out;
     }
 }
 

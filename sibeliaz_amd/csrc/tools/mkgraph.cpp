@@ -121,7 +121,9 @@ void forEachKmer(const std::string& seq, int k, size_t from, size_t to, F fn) {
 }
 
 // --gpu: $LCB_LIB, or libsibeliaz_amd.so next to the bin/ directory of this executable.
-int runOnGpu(const std::vector<std::string>& fasta, int k, int ordinal, unsigned tableLog2, unsigned tileWindows, const std::string& out)
+// partitions < 0: lcb_junctions_build, as before the partitioned build existed; otherwise lcb_junctions_build_ex (0 = automatic).
+int runOnGpu(const std::vector<std::string>& fasta, int k, int ordinal, unsigned tableLog2, unsigned tileWindows, int partitions, unsigned long long memBudget,
+             const std::string& out)
 {
     try {
         std::string lib;
@@ -136,24 +138,38 @@ int runOnGpu(const std::vector<std::string>& fasta, int k, int ordinal, unsigned
         void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
         if (!h) { const char* why = dlerror(); throw std::runtime_error("--gpu: cannot load " + lib + ": " + (why ? why : "unknown reason")); }
         typedef int (*build_fn)(const char* const*, int, int, int, const lcb_junction_opts*, const char*, lcb_junction_stats*);
+        typedef int (*build_ex_fn)(const char* const*, int, int, int, const lcb_junction_opts_ex*, const char*, lcb_junction_stats_ex*);
         typedef const char* (*error_fn)(void);
-        const build_fn build = (build_fn)dlsym(h, "lcb_junctions_build");
+        const bool ex = partitions >= 0;
+        void* const build = dlsym(h, ex ? "lcb_junctions_build_ex" : "lcb_junctions_build");
         const error_fn lastError = (error_fn)dlsym(h, "lcb_last_error");
-        if (!build || !lastError) throw std::runtime_error("--gpu: " + lib + " has no lcb_junctions_build (an older library?)");
+        if (!build || !lastError) throw std::runtime_error("--gpu: " + lib + " has no " + (ex ? "lcb_junctions_build_ex" : "lcb_junctions_build") + " (an older library?)");
         std::vector<const char*> files;
         for (const std::string& f : fasta) files.push_back(f.c_str());
-        lcb_junction_opts o;
-        memset(&o, 0, sizeof(o));
-        o.abi = LCB_ABI_VERSION; o.table_log2 = tableLog2; o.tile_windows = tileWindows;
-        lcb_junction_stats st;
-        memset(&st, 0, sizeof(st));
-        if (build(files.data(), (int)files.size(), k, ordinal, &o, out.c_str(), &st) != LCB_OK) throw std::runtime_error(lastError());
+        lcb_junction_stats_ex sx;
+        memset(&sx, 0, sizeof(sx));
+        lcb_junction_stats& st = sx.base;
+        if (ex) {
+            lcb_junction_opts_ex o;
+            memset(&o, 0, sizeof(o));
+            o.abi = LCB_ABI_VERSION; o.table_log2 = tableLog2; o.tile_windows = tileWindows; o.partitions = (uint32_t)partitions; o.mem_budget = memBudget;
+            if (((build_ex_fn)build)(files.data(), (int)files.size(), k, ordinal, &o, out.c_str(), &sx) != LCB_OK) throw std::runtime_error(lastError());
+        } else {
+            lcb_junction_opts o;
+            memset(&o, 0, sizeof(o));
+            o.abi = LCB_ABI_VERSION; o.table_log2 = tableLog2; o.tile_windows = tileWindows;
+            if (((build_fn)build)(files.data(), (int)files.size(), k, ordinal, &o, out.c_str(), &st) != LCB_OK) throw std::runtime_error(lastError());
+        }
         if (kVerbose) {
             const std::pair<const char*, double> phases[] = {{"read FASTA", st.read_ms}, {"upload (GPU)", st.upload_ms}, {"k-mer table (GPU)", st.insert_ms},
                                                              {"junction occurrences (GPU)", st.emit_ms}, {"records (host, overlapped)", st.write_ms}};
             for (const auto& p : phases) fprintf(stderr, "lcb-mkgraph: %-28s %.2f s\n", p.first, p.second / 1000.0);
             fprintf(stderr, "lcb-mkgraph: gpu: insert %.3f ms, emit %.3f ms, upload %.3f ms; %lld windows, table 2^%d slots after %lld rebuilds, %lld tiles\n", st.insert_ms,
                     st.emit_ms, st.upload_ms, (long long)st.windows, __builtin_ctzll((unsigned long long)st.table_slots), (long long)st.table_rebuilds, (long long)st.tiles);
+            if (ex)
+                fprintf(stderr, "lcb-mkgraph: gpu: %lld partitions in %lld passes, mark %.3f ms; %lld junction windows, junction table %lld slots; peak %llu bytes of device memory\n",
+                        (long long)sx.partitions, (long long)sx.passes, sx.mark_ms, (long long)sx.junction_windows, (long long)sx.junction_table_slots,
+                        (unsigned long long)sx.peak_device_bytes);
         }
         fprintf(stderr, "lcb-mkgraph: %zu records, %llu junction occurrences, %u junction k-mers\n", (size_t)st.records, (unsigned long long)st.occurrences,
                 (unsigned)st.junction_kmers);
@@ -167,8 +183,10 @@ int runOnGpu(const std::vector<std::string>& fasta, int k, int ordinal, unsigned
 }  // namespace
 
 int main(int argc, char** argv) {
-    int k = 25, gpu = -1;
+    int k = 25, gpu = -1, partitions = -1;
     unsigned tableLog2 = 0, tileWindows = 0;
+    unsigned long long memBudget = 0;
+    bool badFlag = false;
     std::string out;
     std::vector<std::string> fasta;
     for (int i = 1; i < argc; i++) {
@@ -178,13 +196,21 @@ int main(int argc, char** argv) {
         else if (a == "--gpu" && i + 1 < argc) gpu = atoi(argv[++i]);
         else if (a == "--table-log2" && i + 1 < argc) tableLog2 = (unsigned)atoi(argv[++i]);
         else if (a == "--tile-windows" && i + 1 < argc) tileWindows = (unsigned)atoi(argv[++i]);
-        else fasta.push_back(a);
+        else if (a == "--partitions" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            partitions = v == "auto" ? 0 : atoi(v.c_str());
+            if (v != "auto" && (partitions < 1 || partitions > 64)) badFlag = true;
+        } else if (a == "--mem-budget" && i + 1 < argc) {
+            memBudget = strtoull(argv[++i], nullptr, 10);
+            if (partitions < 0) partitions = 0;
+        } else fasta.push_back(a);
     }
-    if (out.empty() || fasta.empty() || k < 3 || k > 31 || k % 2 == 0) {
-        fprintf(stderr, "usage: lcb-mkgraph -k <odd 3..31> -o junctions.bin [--gpu <ordinal> [--table-log2 N] [--tile-windows N]] <fasta...>\n");
+    if (out.empty() || fasta.empty() || k < 3 || k > 31 || k % 2 == 0 || badFlag) {
+        fprintf(stderr, "usage: lcb-mkgraph -k <odd 3..31> -o junctions.bin [--gpu <ordinal> [--table-log2 N] [--tile-windows N] [--partitions <1..64|auto>] "
+                        "[--mem-budget BYTES]] <fasta...>\n");
         return 2;
     }
-    if (gpu >= 0) return runOnGpu(fasta, k, gpu, tableLog2, tileWindows, out);
+    if (gpu >= 0) return runOnGpu(fasta, k, gpu, tableLog2, tileWindows, partitions, memBudget, out);
     try {
         double tPhase = nowS();
         std::vector<Record> rec;
