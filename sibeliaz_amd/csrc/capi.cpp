@@ -79,60 +79,62 @@ const uint64_t* lcb_graph_chr_start(const lcb_graph* g) { return g->chrStart.dat
 const int32_t* lcb_graph_pos_id(const lcb_graph* g) { return g->posId.data(); }
 const uint32_t* lcb_graph_pos_pos(const lcb_graph* g) { return g->posPos.data(); }
 
-int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int device_ordinal, const lcb_junction_opts* opts,
-                        const char* out_file, lcb_junction_stats* stats)
+namespace {
+// `name`: the struct the messages name (lcb_junctions_build's options are checked after conversion).
+void checkJunctionOpts(const lcb_junction_opts_ex* opts, const std::string& name)
 {
-    LCB_TRY
-    // everything that can be refused without a device is refused before the device is touched
-    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError("lcb_junctions_build: k must be odd and in 3..31, not " + std::to_string(k));
-    if (!fasta_files || n_fasta < 1) throw LcbError("lcb_junctions_build: no FASTA file");
-    if (!out_file || !*out_file) throw LcbError("lcb_junctions_build: no output file");
-    if (opts && opts->abi != (uint32_t)LCB_ABI_VERSION)
-        throw LcbError("lcb_junction_opts.abi is " + std::to_string(opts->abi) + ", this library has LCB_ABI_VERSION " + std::to_string(LCB_ABI_VERSION));
-    if (opts && opts->table_log2 > 40) throw LcbError("lcb_junction_opts.table_log2 is " + std::to_string(opts->table_log2) + ": at most 40");
-    if (opts && opts->tile_windows > (1u << 30)) throw LcbError("lcb_junction_opts.tile_windows is " + std::to_string(opts->tile_windows) + ": at most 2^30");
+    if (!opts) return;
+    if (opts->abi != (uint32_t)LCB_ABI_VERSION)
+        throw LcbError(name + ".abi is " + std::to_string(opts->abi) + ", this library has LCB_ABI_VERSION " + std::to_string(LCB_ABI_VERSION));
+    if (opts->partitions > 64) throw LcbError(name + ".partitions is " + std::to_string(opts->partitions) + ": at most 64 (0 = automatic)");
+    if (opts->table_log2 > 40) throw LcbError(name + ".table_log2 is " + std::to_string(opts->table_log2) + ": at most 40");
+    if (opts->tile_windows > (1u << 30)) throw LcbError(name + ".tile_windows is " + std::to_string(opts->tile_windows) + ": at most 2^30");
+}
+
+// Everything that can be refused without a device is refused before the device is touched. `fn`: the function the messages name.
+void buildJunctions(const std::string& fn, const std::string& optsName, const char* const* fasta_files, int n_fasta, int k, int device_ordinal,
+                    const lcb_junction_opts_ex& opts, const char* out_file, lcb_junction_stats_ex* stats)
+{
+    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(fn + ": k must be odd and in 3..31, not " + std::to_string(k));
+    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
+    if (!out_file || !*out_file) throw LcbError(fn + ": no output file");
+    checkJunctionOpts(&opts, optsName);
     std::vector<std::string> fa;
     for (int i = 0; i < n_fasta; i++) {
-        if (!fasta_files[i]) throw LcbError("lcb_junctions_build: FASTA path " + std::to_string(i) + " is null");
+        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
         FILE* f = fopen(fasta_files[i], "rb");
-        if (!f) throw LcbError(std::string("lcb_junctions_build: cannot open ") + fasta_files[i]);
+        if (!f) throw LcbError(fn + ": cannot open " + fasta_files[i]);
         fclose(f);
         fa.push_back(fasta_files[i]);
     }
     lcb_junctions_build_impl(fa, k, device_ordinal, opts, out_file, stats);
+}
+}  // namespace
+
+int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int device_ordinal, const lcb_junction_opts* opts,
+                        const char* out_file, lcb_junction_stats* stats)
+{
+    LCB_TRY
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    o.partitions = 1;       // the single-table path
+    if (opts) { o.abi = opts->abi; o.table_log2 = opts->table_log2; o.tile_windows = opts->tile_windows; }
+    lcb_junction_stats_ex x;
+    buildJunctions("lcb_junctions_build", "lcb_junction_opts", fasta_files, n_fasta, k, device_ordinal, o, out_file, &x);
+    if (stats) *stats = x.base;
     return LCB_OK;
     LCB_CATCH(LCB_ERR)
 }
-
-namespace {
-void checkJunctionOptsEx(const lcb_junction_opts_ex* opts)
-{
-    if (!opts) return;
-    if (opts->abi != (uint32_t)LCB_ABI_VERSION)
-        throw LcbError("lcb_junction_opts_ex.abi is " + std::to_string(opts->abi) + ", this library has LCB_ABI_VERSION " + std::to_string(LCB_ABI_VERSION));
-    if (opts->partitions > 64) throw LcbError("lcb_junction_opts_ex.partitions is " + std::to_string(opts->partitions) + ": at most 64 (0 = automatic)");
-    if (opts->table_log2 > 40) throw LcbError("lcb_junction_opts_ex.table_log2 is " + std::to_string(opts->table_log2) + ": at most 40");
-    if (opts->tile_windows > (1u << 30)) throw LcbError("lcb_junction_opts_ex.tile_windows is " + std::to_string(opts->tile_windows) + ": at most 2^30");
-}
-}  // namespace
 
 int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, int device_ordinal, const lcb_junction_opts_ex* opts,
                            const char* out_file, lcb_junction_stats_ex* stats)
 {
     LCB_TRY
-    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError("lcb_junctions_build_ex: k must be odd and in 3..31, not " + std::to_string(k));
-    if (!fasta_files || n_fasta < 1) throw LcbError("lcb_junctions_build_ex: no FASTA file");
-    if (!out_file || !*out_file) throw LcbError("lcb_junctions_build_ex: no output file");
-    checkJunctionOptsEx(opts);
-    std::vector<std::string> fa;
-    for (int i = 0; i < n_fasta; i++) {
-        if (!fasta_files[i]) throw LcbError("lcb_junctions_build_ex: FASTA path " + std::to_string(i) + " is null");
-        FILE* f = fopen(fasta_files[i], "rb");
-        if (!f) throw LcbError(std::string("lcb_junctions_build_ex: cannot open ") + fasta_files[i]);
-        fclose(f);
-        fa.push_back(fasta_files[i]);
-    }
-    lcb_junctions_build_ex_impl(fa, k, device_ordinal, opts, out_file, stats);
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    buildJunctions("lcb_junctions_build_ex", "lcb_junction_opts_ex", fasta_files, n_fasta, k, device_ordinal, opts ? *opts : o, out_file, stats);
     return LCB_OK;
     LCB_CATCH(LCB_ERR)
 }
@@ -140,7 +142,7 @@ int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, i
 int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget, int32_t* partitions, uint64_t* need_bytes)
 {
     LCB_TRY
-    checkJunctionOptsEx(opts);
+    checkJunctionOpts(opts, "lcb_junction_opts_ex");
     lcb_junctions_plan_impl(windows, seq_bytes, opts, budget, partitions, need_bytes);
     return LCB_OK;
     LCB_CATCH(LCB_ERR)

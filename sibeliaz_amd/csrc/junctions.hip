@@ -101,13 +101,65 @@ struct Run {
         p = nullptr;
         live -= bytes;
     }
+    // One timed step: `work` (launches and memsets on the stream) between two events, the state block to the host behind it, `meanwhile`
+    // on the host while the device works, and the device time of the step added to a phase.
+    template <class W, class H = void (*)()>
+    void timed(double& phaseMs, W work, H meanwhile = [] {})
+    {
+        HIP_CHECK(hipEventRecord(evA, stream));
+        work();
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(evB, stream));
+        HIP_CHECK(hipMemcpyAsync(hState, dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, stream));
+        meanwhile();
+        HIP_CHECK(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, evA, evB));
+        phaseMs += ms;
+    }
+};
+
+// The junction file, written while the device works on the next tile: the records of a tile, with the separators of the sequences
+// that end in front of them.
+struct Writer {
+    Run& R;
+    const std::vector<uint64_t>&base, &recLen;
+    double& writeMs;
+    std::vector<unsigned char> buf;
+    size_t curRec = 0;
+    void flushBuf()
+    {
+        if (!buf.empty() && fwrite(buf.data(), 1, buf.size(), R.f) != buf.size()) throw LcbError("cannot write " + R.part);
+        buf.clear();
+    }
+    void put(uint32_t pos, int64_t id)
+    {
+        const size_t at = buf.size();
+        buf.resize(at + 12);
+        memcpy(&buf[at], &pos, 4); memcpy(&buf[at + 4], &id, 8);
+        if (buf.size() >= (64u << 20)) flushBuf();
+    }
+    void drain(int slot, uint64_t n)
+    {
+        HIP_CHECK(hipEventSynchronize(R.evCopy[slot]));
+        const double t0 = nowMs();
+        const JRecord* o = R.hOut[slot];
+        for (uint64_t q = 0; q < n; q++) {
+            while (o[q].g >= base[curRec] + recLen[curRec]) { put(0xFFFFFFFFu, INT64_MAX); curRec++; }
+            put((uint32_t)(o[q].g - base[curRec]), (int64_t)o[q].id);
+        }
+        flushBuf();
+        writeMs += nowMs() - t0;
+    }
 };
 
 static_assert(sizeof(JState) + sizeof(unsigned long long) <= LCB_JUNCTION_STATE_BYTES, "the state block holds the JState and the count of marked windows");
 
-// P == 1: the single-table path. P == 0: as many partitions as lcb_junctions_plan finds for the budget. Otherwise P partitions.
-void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t tableLog2, uint32_t tileWindowsOpt, uint32_t P, uint64_t budgetOpt,
-           const std::string& outFile, lcb_junction_stats_ex* stats)
+}  // namespace
+
+// opts.partitions == 1: the single-table path. 0: as many partitions as lcb_junctions_plan finds for the budget. Otherwise that many.
+void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex& opts, const std::string& outFile,
+                              lcb_junction_stats_ex* stats)
 {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
@@ -116,6 +168,8 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
     lcb_junction_stats_ex X;
     memset(&X, 0, sizeof(X));
     lcb_junction_stats& S = X.base;
+    const uint32_t tableLog2 = opts.table_log2;
+    uint32_t P = opts.partitions;
 
     // ---- read + encode (in place: the sequence strings become the code bytes)
     double t = nowMs();
@@ -123,12 +177,13 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
     for (const std::string& f : fasta) {
         try { lcb_fasta::readFasta(f, rec); } catch (std::exception& e) { throw LcbError(e.what()); }
     }
-    std::vector<uint64_t> base(rec.size() + 1);
+    std::vector<uint64_t> base(rec.size() + 1), recLen(rec.size());
     uint64_t len = 1, nWindows = 0;
     for (size_t r = 0; r < rec.size(); r++) {
         base[r] = len;
-        len += rec[r].seq.size() + 1;
-        if (rec[r].seq.size() >= (size_t)k) nWindows += rec[r].seq.size() - k + 1;
+        recLen[r] = rec[r].seq.size();
+        len += recLen[r] + 1;
+        if (recLen[r] >= (size_t)k) nWindows += recLen[r] - k + 1;
     }
     base[rec.size()] = len;
     for (lcb_fasta::Record& r : rec) {
@@ -141,13 +196,13 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
     S.windows = (int64_t)nWindows;
     S.read_ms = nowMs() - t;
 
-    // ---- the budget, the number of partitions, and whether the first phase fits, before anything is allocated
+    // ---- plan: the budget, the number of partitions, and whether the first phase fits, before anything is allocated
     Run R;
     HIP_CHECK(hipSetDevice(ordinal));
     size_t freeB = 0, totalB = 0;
     HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-    R.budget = budgetOpt ? std::min<uint64_t>(budgetOpt, freeB) : (uint64_t)freeB;
-    const uint32_t tileWindows = tileWindowsOpt ? tileWindowsOpt : (1u << 22);
+    R.budget = opts.mem_budget ? std::min<uint64_t>(opts.mem_budget, freeB) : (uint64_t)freeB;
+    const uint32_t tileWindows = opts.tile_windows ? opts.tile_windows : (1u << 22);
     const uint32_t tileBuf = (uint32_t)std::min<uint64_t>(tileWindows, len);
     const uint32_t nbMax = gridFor(tileBuf, JT);
     const uint64_t tileBytes = (uint64_t)tileBuf * (sizeof(unsigned long long) + sizeof(JRecord)) + (uint64_t)nbMax * 8;
@@ -160,7 +215,7 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
         lcb_junctions_plan_impl((int64_t)nWindows, (int64_t)len, &o, R.budget, &planned, nullptr);
         P = (uint32_t)planned;
     }
-    uint32_t capLog2 = tableLog2 ? tableLog2 : lcb_junction_default_log2(nWindows, P);
+    const uint32_t capLog2 = tableLog2 ? tableLog2 : lcb_junction_default_log2(nWindows, P);
     const uint64_t need = P == 1 ? len + tileBytes + LCB_JUNCTION_STATE_BYTES + lcb_junction_table_bytes(capLog2) : lcb_junction_phase_a_bytes(nWindows, len, tableLog2, P);
     if (need > R.budget)
         throw LcbError("lcb_junctions_build: the input needs " + std::to_string(need) + " bytes of device memory with " + std::to_string(P) + " partition(s), " +
@@ -183,9 +238,9 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
     };
     if (P == 1) allocTiles();
     HIP_CHECK(hipHostMalloc((void**)&R.hState, LCB_JUNCTION_STATE_BYTES, hipHostMallocDefault));
-    float ms = 0;
 
     // ---- upload
+    float ms = 0;
     HIP_CHECK(hipEventRecord(R.evA, R.stream));
     HIP_CHECK(hipMemsetAsync(R.dCodes, 4, len, R.stream));
     HIP_CHECK(hipMemsetAsync(R.dState, 0, LCB_JUNCTION_STATE_BYTES, R.stream));
@@ -196,50 +251,41 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
     HIP_CHECK(hipEventSynchronize(R.evB));
     HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
     S.upload_ms = ms;
-    std::vector<uint64_t> recLen(rec.size());
-    for (size_t r = 0; r < rec.size(); r++) recLen[r] = rec[r].seq.size();
     std::vector<lcb_fasta::Record>().swap(rec);      // (the host copy of the sequence is no longer needed)
 
-    // One attempt to fill a fresh table of 2^log2 slots with `insert` (a launch on R.stream); false: too full, the table is freed again.
+    // ---- table(s). One attempt to fill a fresh table of 2^log2 slots with `insert` (a launch on R.stream); false: too full, the
+    // table is freed again.
     uint64_t mask = 0;
-    auto tryTable = [&](uint32_t log2, const char* what, double& phaseMs, auto insert) {
+    auto tryTable = [&](uint32_t log2, const std::string& what, double& phaseMs, auto insert) {
         const uint64_t cap = 1ull << log2;
         mask = cap - 1;
-        R.alloc(R.dKey, cap * sizeof(unsigned long long), what);
-        R.alloc(R.dVal, cap * sizeof(uint32_t), what);
-        HIP_CHECK(hipEventRecord(R.evA, R.stream));
-        HIP_CHECK(hipMemsetAsync(R.dKey, 0, cap * sizeof(unsigned long long), R.stream));
-        HIP_CHECK(hipMemsetAsync(R.dVal, 0, cap * sizeof(uint32_t), R.stream));
-        HIP_CHECK(hipMemsetAsync(R.dState, 0, sizeof(JState), R.stream));
-        insert();
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(R.evB, R.stream));
-        HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, R.stream));
-        HIP_CHECK(hipStreamSynchronize(R.stream));
-        float e = 0;
-        HIP_CHECK(hipEventElapsedTime(&e, R.evA, R.evB));
-        phaseMs += e;
+        R.alloc(R.dKey, cap * sizeof(unsigned long long), what.c_str());
+        R.alloc(R.dVal, cap * sizeof(uint32_t), what.c_str());
+        R.timed(phaseMs, [&]() {
+            HIP_CHECK(hipMemsetAsync(R.dKey, 0, cap * sizeof(unsigned long long), R.stream));
+            HIP_CHECK(hipMemsetAsync(R.dVal, 0, cap * sizeof(uint32_t), R.stream));
+            HIP_CHECK(hipMemsetAsync(R.dState, 0, sizeof(JState), R.stream));
+            insert();
+        });
         if (!R.hState->full && R.hState->used * 10 <= cap * 9) return true;
         S.table_rebuilds++;
         R.release(R.dKey, cap * sizeof(unsigned long long));
         R.release(R.dVal, cap * sizeof(uint32_t));
         return false;
     };
-    auto freeTable = [&]() {
-        R.release(R.dKey, (mask + 1) * sizeof(unsigned long long));
-        R.release(R.dVal, (mask + 1) * sizeof(uint32_t));
+    // A table that may take whatever it needs: too full -> twice the slots, from the start.
+    auto growTable = [&](uint32_t log2, const std::string& name, const char* note, double& phaseMs, auto insert) {
+        for (;; log2++) {
+            if (log2 > 40) throw LcbError("lcb_junctions_build: " + name + " would need more than 2^40 slots");
+            if (tryTable(log2, name + note, phaseMs, insert)) return;
+        }
     };
     const uint32_t gridAll = gridFor(len, J_WPB);
     unsigned long long* const dMarked = (unsigned long long*)((char*)R.dState + sizeof(JState));
 
     if (P == 1) {
-        // ---- the k-mer table: insert everything; too full -> twice the slots, from the start
-        for (;; capLog2++) {
-            if (capLog2 > 40) throw LcbError("lcb_junctions_build: the k-mer table would need more than 2^40 slots");
-            if (tryTable(capLog2, "the k-mer table", S.insert_ms,
-                         [&]() { junctionInsert<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, R.dState); }))
-                break;
-        }
+        growTable(capLog2, "the k-mer table", "", S.insert_ms,
+                  [&]() { junctionInsert<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, R.dState); });
         S.table_slots = (int64_t)(mask + 1);
         X.passes = 1;
     } else {
@@ -269,81 +315,44 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
             }
             if (split) continue;
             S.table_slots = std::max<int64_t>(S.table_slots, (int64_t)(mask + 1));
-            HIP_CHECK(hipEventRecord(R.evA, R.stream));
-            junctionMarkPart<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, q.M, q.r, R.dBitmap, dMarked, R.dState);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventRecord(R.evB, R.stream));
-            HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, R.stream));
-            HIP_CHECK(hipStreamSynchronize(R.stream));
-            HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
-            X.mark_ms += ms;
+            R.timed(X.mark_ms, [&]() {
+                junctionMarkPart<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, q.M, q.r, R.dBitmap, dMarked, R.dState);
+            });
             if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a k-mer of the input is missing from the table of its partition");
-            freeTable();
+            R.release(R.dKey, (mask + 1) * sizeof(unsigned long long));
+            R.release(R.dVal, (mask + 1) * sizeof(uint32_t));
             X.passes++;
         }
         // ---- phase B: the table of the junction k-mers (every key of it is a junction), then the tiles as with one table
         const uint64_t nJ = *(const unsigned long long*)((const char*)R.hState + sizeof(JState));
         X.junction_windows = (int64_t)nJ;
         allocTiles();
-        uint32_t jLog2 = lcb_junction_default_log2(nJ, 1);
-        for (;; jLog2++) {
-            if (jLog2 > 40) throw LcbError("lcb_junctions_build: the table of junction k-mers would need more than 2^40 slots");
-            if (tryTable(jLog2, "the table of junction k-mers (phase B is not partitioned)", S.emit_ms,
-                         [&]() { junctionFillMarked<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, R.dState); }))
-                break;
-        }
+        growTable(lcb_junction_default_log2(nJ, 1), "the table of junction k-mers", " (phase B is not partitioned)", S.emit_ms,
+                  [&]() { junctionFillMarked<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, R.dState); });
         if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a marked position holds no window");
         X.junction_table_slots = (int64_t)(mask + 1);
     }
 
-    // ---- classify + emit, tile by tile in file order; the host turns tile t - 1 into records while the device works on tile t
+    // ---- tiles: classify + emit in file order; the host turns tile t - 1 into records while the device works on tile t
     HIP_CHECK(hipHostMalloc((void**)&R.hOut[0], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
     HIP_CHECK(hipHostMalloc((void**)&R.hOut[1], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
     R.part = outFile + ".part";
     R.f = fopen(R.part.c_str(), "wb");
     if (!R.f) { const std::string p = R.part; R.part.clear(); throw LcbError("cannot create " + p); }
-    std::vector<unsigned char> buf;
-    auto flushBuf = [&]() {
-        if (!buf.empty() && fwrite(buf.data(), 1, buf.size(), R.f) != buf.size()) throw LcbError("cannot write " + R.part);
-        buf.clear();
-    };
-    auto put = [&](uint32_t pos, int64_t id) {
-        const size_t at = buf.size();
-        buf.resize(at + 12);
-        memcpy(&buf[at], &pos, 4); memcpy(&buf[at + 4], &id, 8);
-        if (buf.size() >= (64u << 20)) flushBuf();
-    };
-    size_t curRec = 0;
-    auto drain = [&](int slot, uint64_t n) {          // the records of one tile, with the separators of the sequences that end in front of them
-        HIP_CHECK(hipEventSynchronize(R.evCopy[slot]));
-        const double t0 = nowMs();
-        const JRecord* o = R.hOut[slot];
-        for (uint64_t q = 0; q < n; q++) {
-            while (o[q].g >= base[curRec] + recLen[curRec]) { put(0xFFFFFFFFu, INT64_MAX); curRec++; }
-            put((uint32_t)(o[q].g - base[curRec]), (int64_t)o[q].id);
-        }
-        flushBuf();
-        S.write_ms += nowMs() - t0;
-    };
+    Writer W{R, base, recLen, S.write_ms};
     uint64_t prevN = 0, ids = 0;
     int64_t tile = 0;
     for (uint64_t t0 = 0; t0 < len; t0 += tileWindows, tile++) {
         const uint32_t tileLen = (uint32_t)std::min<uint64_t>(tileWindows, len - t0);
-        const uint32_t nb = gridFor(tileLen, JT);
-        HIP_CHECK(hipEventRecord(R.evA, R.stream));
-        if (P == 1) junctionClassify<<<gridFor(tileLen, J_WPB), JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
-        else junctionClassifyMarked<<<gridFor(tileLen, J_WPB), JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
-        junctionMarkFirst<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, R.dCntF);
-        junctionScan<<<1, 1024, 0, R.stream>>>(R.dCntJ, R.dCntF, nb, R.dState);
-        junctionAssignIds<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntF, R.dState);
-        junctionEmit<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, t0, R.dOut);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(R.evB, R.stream));
-        HIP_CHECK(hipMemcpyAsync(R.hState, R.dState, LCB_JUNCTION_STATE_BYTES, hipMemcpyDeviceToHost, R.stream));
-        if (tile > 0) drain((int)((tile - 1) & 1), prevN);
-        HIP_CHECK(hipStreamSynchronize(R.stream));
-        HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
-        S.emit_ms += ms;
+        const uint32_t nb = gridFor(tileLen, JT), nbRun = gridFor(tileLen, J_WPB);
+        R.timed(S.emit_ms, [&]() {
+            if (P == 1) junctionClassify<<<nbRun, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
+            else junctionClassifyMarked<<<nbRun, JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, t0, tileLen, R.dWslot, R.dState);
+            junctionMarkFirst<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, R.dCntF);
+            junctionScan<<<1, 1024, 0, R.stream>>>(R.dCntJ, R.dCntF, nb, R.dState);
+            junctionAssignIds<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntF, R.dState);
+            junctionEmit<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, t0, R.dOut);
+        }, [&]() { if (tile > 0) W.drain((int)((tile - 1) & 1), prevN); });
         if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a k-mer of the input is missing from the table");
         prevN = R.hState->totJ;
         ids = R.hState->idNext;
@@ -353,12 +362,14 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
         HIP_CHECK(hipEventRecord(R.evCopy[tile & 1], R.stream));
         S.occurrences += (int64_t)prevN;
     }
-    if (tile > 0) drain((int)((tile - 1) & 1), prevN);
+    if (tile > 0) W.drain((int)((tile - 1) & 1), prevN);
     if (P == 1) X.junction_windows = S.occurrences;
     else if (S.occurrences != X.junction_windows) throw LcbError("lcb_junctions_build: internal error: the tiles found another number of junction windows than the passes marked");
+
+    // ---- finish: the separators of the sequences behind the last record, and the file under its name
     const double tw = nowMs();
-    for (; curRec < recLen.size(); curRec++) put(0xFFFFFFFFu, INT64_MAX);
-    flushBuf();
+    for (; W.curRec < recLen.size(); W.curRec++) W.put(0xFFFFFFFFu, INT64_MAX);
+    W.flushBuf();
     FILE* f = R.f;
     R.f = nullptr;
     if (fclose(f) != 0) throw LcbError("cannot write " + R.part);
@@ -369,20 +380,4 @@ void build(const std::vector<std::string>& fasta, int k, int ordinal, uint32_t t
     S.tiles = tile;
     X.peak_device_bytes = R.peak;
     if (stats) *stats = X;
-}
-
-}  // namespace
-
-void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts* opts, const std::string& outFile,
-                              lcb_junction_stats* stats)
-{
-    lcb_junction_stats_ex X;
-    build(fasta, k, ordinal, opts ? opts->table_log2 : 0, opts ? opts->tile_windows : 0, 1, 0, outFile, &X);
-    if (stats) *stats = X.base;
-}
-
-void lcb_junctions_build_ex_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex* opts, const std::string& outFile,
-                                 lcb_junction_stats_ex* stats)
-{
-    build(fasta, k, ordinal, opts ? opts->table_log2 : 0, opts ? opts->tile_windows : 0, opts ? opts->partitions : 0, opts ? opts->mem_budget : 0, outFile, stats);
 }

@@ -39,10 +39,8 @@ void lcb_set_error(const std::string& msg);
 // graph.cpp
 lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::string>& fasta, int k, int abundance, int threads);
 // junctions.hip — GPU junction finder (byte-identical to tools/mkgraph.cpp); arguments are already validated
-void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts* opts, const std::string& outFile,
-                              lcb_junction_stats* stats);
-void lcb_junctions_build_ex_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex* opts, const std::string& outFile,
-                                 lcb_junction_stats_ex* stats);
+void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex& opts, const std::string& outFile,
+                              lcb_junction_stats_ex* stats);
 // junction_plan.cpp — the memory arithmetic of the partitioned build (no device): what lcb_junctions_plan answers and junctions.hip obeys
 constexpr uint64_t LCB_JUNCTION_STATE_BYTES = 64;      // the device-side state block (JState + the count of marked windows)
 uint64_t lcb_junction_table_bytes(uint32_t log2);      // 12 bytes per slot

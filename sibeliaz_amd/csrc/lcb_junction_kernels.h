@@ -1,5 +1,8 @@
 // lcb_junction_kernels.h — device code of the GPU junction finder (host driver: junctions.hip). Kept in a header of its
-// own so that the wavefront emulator of tests/emu can compile and run the same kernels on the CPU (tests/test_junctions_emu.py).
+// own so that the wavefront emulator of tests/emu can compile and run the same kernels on the CPU (tests/test_junctions_emu.py,
+// tests/test_junction_partitions_emu.py). The table is probed in two places (jFind, jClaim); the single-table and the partitioned
+// build share one insert body (jInsertBody<J_ALL | J_PART | J_MARKED>), one classify body (jClassifyBody<marked>) and the
+// four tile kernels behind it; junctionMarkPart belongs to the partitioned build alone.
 #ifndef LCB_JUNCTION_KERNELS_H
 #define LCB_JUNCTION_KERNELS_H
 
@@ -112,11 +115,62 @@ __device__ __forceinline__ uint32_t jBlockExScan(uint32_t v, uint32_t& total)
     return base + inc - v;
 }
 
-// Every window of the input into the table. A plain load first, the atomic only if it would change something: most occurrences repeat
-// what the slot already says. A plain load may be stale (the L2s of the XCDs are not coherent): an empty key that is no longer empty
-// is settled by the compare-and-swap's return value, missing mask bits cost one atomicOr that changes nothing. No lane waits for another.
-__global__ __launch_bounds__(JT) void junctionInsert(const uint8_t* __restrict__ codes, uint64_t len, int k, unsigned long long* key, uint32_t* val,
-                                                     uint64_t mask, JState* st)
+// ---- the two probe loops: linear from jMix(kmer) & mask, key = kmer + 1 (0 = empty). Find only, after a complete insertion (the
+// launches in front have ended, so plain loads see every key). true: key[h] holds the k-mer.
+__device__ __forceinline__ bool jFind(const unsigned long long* __restrict__ key, uint64_t mask, uint64_t kmer, uint64_t& h)
+{
+    const unsigned long long want = kmer + 1;
+    h = jMix(kmer) & mask;
+    bool found = false;
+    for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
+        const unsigned long long cur = key[h];
+        if (cur == want) { found = true; break; }
+        if (cur == 0) break;
+    }
+    return found;
+}
+
+// Claim or find, and OR `bits` into the slot's mask. A plain load first, the atomic only if it would change something: most occurrences
+// repeat what the slot already says. A plain load may be stale (the L2s of the XCDs are not coherent): an empty key that is no longer
+// empty is settled by the compare-and-swap's return value, missing mask bits cost one atomicOr that changes nothing. No lane waits for
+// another. `claimed` counts the slots this lane took. false: no place within the table, or somebody raised st->full (looked at every
+// 256 probes) - the table must be given up. (One exit from each loop: with a return inside, the compiler keeps a three-way state.)
+__device__ __forceinline__ bool jClaim(unsigned long long* key, uint32_t* val, uint64_t mask, uint64_t kmer, uint32_t bits, uint32_t& claimed, const JState* st)
+{
+    const unsigned long long want = kmer + 1;
+    uint64_t h = jMix(kmer) & mask;
+    bool done = false;
+    for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
+        unsigned long long cur = key[h];
+        if (cur == 0) {
+            cur = atomicCAS(&key[h], 0ull, want);
+            if (cur == 0) { claimed++; cur = want; }
+        }
+        if (cur == want) {
+            if ((val[h] & bits) != bits) atomicOr(&val[h], bits);
+            done = true;
+            break;
+        }
+        if ((probes & 255) == 255 && __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+    }
+    return done;
+}
+
+__device__ __forceinline__ bool jMarked(const unsigned long long* __restrict__ bitmap, uint64_t g) { return (bitmap[g >> 6] >> (g & 63)) & 1ull; }
+
+// ---- the insert kernels: one body, the windows it takes chosen at compile time (the single-table path pays for no % P and no bitmap load).
+//   J_ALL      every window of the input: the single table (junctionInsert)
+//   J_PART     the windows with jPartition(kmer, P) == p: the table of one pass of the partitioned build (junctionInsertPart)
+//   J_MARKED   the windows with a bit in bitmap[], with 0x100 | the window's bits: the table of junction k-mers (junctionFillMarked) - jIsJunction holds for
+//              every key of it; a bit without a window cannot happen and sets `lost`
+// bitmap, P and p are read by the selection that needs them only.
+// The `full` protocol: nobody starts a window once st->full is up; a lane whose probe gives up raises it; the workgroup adds its claimed
+// slots to st->used once and raises it beyond 0.9 of the slots. The host then starts over with twice the slots.
+enum JSelect { J_ALL, J_PART, J_MARKED };
+
+template <JSelect SEL>
+__device__ __forceinline__ void jInsertBody(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ bitmap,
+                                            unsigned long long* key, uint32_t* val, uint64_t mask, JState* st, uint32_t P, uint32_t p)
 {
     __shared__ uint8_t s[J_WPB + 40];
     __shared__ uint32_t claimed;
@@ -128,26 +182,14 @@ __global__ __launch_bounds__(JT) void junctionInsert(const uint8_t* __restrict__
     bool stop = __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
     for (int j = 0; j < J_RUN && !stop; j++) {
         const int w = j * JT + threadIdx.x;
-        if (b0 + (uint64_t)w >= len) break;
+        const uint64_t g = b0 + (uint64_t)w;
+        if (g >= len) break;
+        if constexpr (SEL == J_MARKED) if (!jMarked(bitmap, g)) continue;
         uint64_t kmer; bool isFwd; uint32_t bits;
-        if (!jWindow(s + w, k, kmer, isFwd, bits)) continue;
-        const unsigned long long want = kmer + 1;
-        uint64_t h = jMix(kmer) & mask;
-        bool done = false;
-        for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
-            unsigned long long cur = key[h];
-            if (cur == 0) {
-                cur = atomicCAS(&key[h], 0ull, want);
-                if (cur == 0) { mine++; cur = want; }
-            }
-            if (cur == want) {
-                if ((val[h] & bits) != bits) atomicOr(&val[h], bits);
-                done = true;
-                break;
-            }
-            if ((probes & 255) == 255 && __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        }
-        if (!done) { atomicOr(&st->full, 1u); stop = true; }
+        if (!jWindow(s + w, k, kmer, isFwd, bits)) { if constexpr (SEL == J_MARKED) atomicOr(&st->lost, 1u); continue; }
+        if constexpr (SEL == J_PART) if (jPartition(kmer, P) != p) continue;
+        if constexpr (SEL == J_MARKED) bits |= 0x100u;
+        if (!jClaim(key, val, mask, kmer, bits, mine, st)) { atomicOr(&st->full, 1u); stop = true; }
     }
     if (mine) atomicAdd(&claimed, mine);
     __syncthreads();
@@ -157,9 +199,19 @@ __global__ __launch_bounds__(JT) void junctionInsert(const uint8_t* __restrict__
     }
 }
 
-// Tile [t0, t0 + tileLen): wslot[i] = slot | strand of window t0 + i if its k-mer is a junction, and the first-occurrence vote.
-__global__ __launch_bounds__(JT) void junctionClassify(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ key,
-                                                       uint32_t* val, uint64_t mask, uint64_t t0, uint32_t tileLen, unsigned long long* wslot, JState* st)
+__global__ __launch_bounds__(JT) void junctionInsert(const uint8_t* __restrict__ codes, uint64_t len, int k, unsigned long long* key, uint32_t* val,
+                                                     uint64_t mask, JState* st)
+{
+    jInsertBody<J_ALL>(codes, len, k, nullptr, key, val, mask, st, 1, 0);
+}
+
+// ---- the classify kernels: tile [t0, t0 + tileLen): wslot[i] = slot | strand of window t0 + i if its k-mer is a junction, and the
+// first-occurrence vote. MARKED (in front of the table of junction k-mers, bitmap[] as above): a window without a bit is W_NONE
+// without a probe, every key is a junction (its value carries 0x100), and a bit without a window sets `lost` like a miss.
+template <bool MARKED>
+__device__ __forceinline__ void jClassifyBody(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ bitmap,
+                                              const unsigned long long* __restrict__ key, uint32_t* val, uint64_t mask, uint64_t t0, uint32_t tileLen,
+                                              unsigned long long* wslot, JState* st)
 {
     __shared__ uint8_t s[J_WPB + 40];
     const uint32_t i0 = blockIdx.x * (uint32_t)J_WPB;
@@ -170,30 +222,28 @@ __global__ __launch_bounds__(JT) void junctionClassify(const uint8_t* __restrict
         const uint32_t i = i0 + (uint32_t)w;
         if (i >= tileLen) break;
         unsigned long long out = W_NONE;
-        uint64_t kmer; bool isFwd; uint32_t bits;
-        if (jWindow(s + w, k, kmer, isFwd, bits)) {
-            const unsigned long long want = kmer + 1;
-            uint64_t h = jMix(kmer) & mask;
-            bool found = false;
-            for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
-                const unsigned long long cur = key[h];
-                if (cur == want) { found = true; break; }
-                if (cur == 0) break;
-            }
-            if (!found) atomicOr(&st->lost, 1u);
-            else {
+        if (!MARKED || jMarked(bitmap, t0 + i)) {
+            uint64_t kmer, h; bool isFwd; uint32_t bits;
+            const bool window = jWindow(s + w, k, kmer, isFwd, bits);
+            if (window && jFind(key, mask, kmer, h)) {
                 // (a stale plain load shows an older = smaller value: at worst an atomicMax that changes nothing)
                 const uint32_t v = val[h], vote = V_PEND | (V_IDX - i);
                 bool junction = true;
                 if (v & V_ID) {}
                 else if (v & V_PEND) { if (v < vote) atomicMax(&val[h], vote); }
-                else if (jIsJunction(v)) atomicMax(&val[h], vote);
+                else if (MARKED || jIsJunction(v)) atomicMax(&val[h], vote);
                 else junction = false;
                 if (junction) out = h | (isFwd ? W_FWD : 0ull);
-            }
+            } else if (MARKED || window) atomicOr(&st->lost, 1u);
         }
         wslot[i] = out;
     }
+}
+
+__global__ __launch_bounds__(JT) void junctionClassify(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ key,
+                                                       uint32_t* val, uint64_t mask, uint64_t t0, uint32_t tileLen, unsigned long long* wslot, JState* st)
+{
+    jClassifyBody<false>(codes, len, k, nullptr, key, val, mask, t0, tileLen, wslot, st);
 }
 
 // One window per lane from here on: workgroup b holds windows [256 b, 256 b + 256) of the tile, so scans over workgroups are in file order.
@@ -261,54 +311,15 @@ __global__ __launch_bounds__(JT) void junctionEmit(const unsigned long long* __r
         out[offJ[blockIdx.x] + rank] = JRecord{t0 + i, (w & W_FWD) ? id : -id};
     }
 }
-
 // ---- the partitioned build (DESIGN.md §10 "Partitioned passes"): the table of pass p holds the k-mers with jPartition(kmer, P) == p only.
 // All occurrences of a k-mer, on both strands, share the canonical form and so the pass: its masks are complete there. What survives a
 // pass is one bit per position of the code array (bit g = window g is a junction occurrence); ids come from a second table that
-// holds the junction k-mers alone.
+// holds the junction k-mers alone (junctionFillMarked), through junctionClassifyMarked and the rest of the tile pipeline as it is.
 
-// junctionInsert restricted to the windows of partition p.
 __global__ __launch_bounds__(JT) void junctionInsertPart(const uint8_t* __restrict__ codes, uint64_t len, int k, unsigned long long* key, uint32_t* val,
                                                          uint64_t mask, JState* st, uint32_t P, uint32_t p)
 {
-    __shared__ uint8_t s[J_WPB + 40];
-    __shared__ uint32_t claimed;
-    const uint64_t b0 = (uint64_t)blockIdx.x * J_WPB;
-    if (threadIdx.x == 0) claimed = 0;
-    jLoadCodes(s, codes, len, b0, k);
-    __syncthreads();
-    uint32_t mine = 0;
-    bool stop = __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    for (int j = 0; j < J_RUN && !stop; j++) {
-        const int w = j * JT + threadIdx.x;
-        if (b0 + (uint64_t)w >= len) break;
-        uint64_t kmer; bool isFwd; uint32_t bits;
-        if (!jWindow(s + w, k, kmer, isFwd, bits)) continue;
-        if (jPartition(kmer, P) != p) continue;
-        const unsigned long long want = kmer + 1;
-        uint64_t h = jMix(kmer) & mask;
-        bool done = false;
-        for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
-            unsigned long long cur = key[h];
-            if (cur == 0) {
-                cur = atomicCAS(&key[h], 0ull, want);
-                if (cur == 0) { mine++; cur = want; }
-            }
-            if (cur == want) {
-                if ((val[h] & bits) != bits) atomicOr(&val[h], bits);
-                done = true;
-                break;
-            }
-            if ((probes & 255) == 255 && __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        }
-        if (!done) { atomicOr(&st->full, 1u); stop = true; }
-    }
-    if (mine) atomicAdd(&claimed, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && claimed) {
-        const unsigned long long u = atomicAdd(&st->used, (unsigned long long)claimed) + claimed;
-        if (u * 10 > (mask + 1) * 9) atomicOr(&st->full, 1u);
-    }
+    jInsertBody<J_PART>(codes, len, k, nullptr, key, val, mask, st, P, p);
 }
 
 // After a complete insertion of partition p: bit g of bitmap[] for every window g of the partition whose k-mer is a junction. Window
@@ -331,18 +342,10 @@ __global__ __launch_bounds__(JT) void junctionMarkPart(const uint8_t* __restrict
         const int w = j * JT + threadIdx.x;
         const uint64_t g = b0 + (uint64_t)w;
         bool junction = false;
-        uint64_t kmer; bool isFwd; uint32_t bits;
+        uint64_t kmer, h; bool isFwd; uint32_t bits;
         if (g < len && jWindow(s + w, k, kmer, isFwd, bits) && jPartition(kmer, P) == p) {
-            const unsigned long long want = kmer + 1;
-            uint64_t h = jMix(kmer) & mask;
-            bool hit = false;
-            for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
-                const unsigned long long cur = key[h];
-                if (cur == want) { hit = true; break; }
-                if (cur == 0) break;
-            }
-            if (!hit) atomicOr(&st->lost, 1u);
-            else junction = jIsJunction(val[h]);
+            if (jFind(key, mask, kmer, h)) junction = jIsJunction(val[h]);
+            else atomicOr(&st->lost, 1u);
         }
         const unsigned long long b = __ballot(junction);
         if (b != 0 && (threadIdx.x & 63) == 0) {    // (b != 0: a window of this word lies inside the array, so the word exists)
@@ -355,93 +358,17 @@ __global__ __launch_bounds__(JT) void junctionMarkPart(const uint8_t* __restrict
     if (threadIdx.x == 0 && found) atomicAdd(marked, (unsigned long long)found);
 }
 
-// The junction table: the k-mer of every window with a bit, with 0x100 | the window's bits - jIsJunction holds for every key of it.
-// The same probing and the same `full` protocol as junctionInsert.
 __global__ __launch_bounds__(JT) void junctionFillMarked(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ bitmap,
                                                          unsigned long long* key, uint32_t* val, uint64_t mask, JState* st)
 {
-    __shared__ uint8_t s[J_WPB + 40];
-    __shared__ uint32_t claimed;
-    const uint64_t b0 = (uint64_t)blockIdx.x * J_WPB;
-    if (threadIdx.x == 0) claimed = 0;
-    jLoadCodes(s, codes, len, b0, k);
-    __syncthreads();
-    uint32_t mine = 0;
-    bool stop = __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    for (int j = 0; j < J_RUN && !stop; j++) {
-        const int w = j * JT + threadIdx.x;
-        const uint64_t g = b0 + (uint64_t)w;
-        if (g >= len) break;
-        if (!((bitmap[g >> 6] >> (g & 63)) & 1ull)) continue;
-        uint64_t kmer; bool isFwd; uint32_t bits;
-        if (!jWindow(s + w, k, kmer, isFwd, bits)) { atomicOr(&st->lost, 1u); continue; }     // (a bit without a window: cannot happen)
-        bits |= 0x100u;
-        const unsigned long long want = kmer + 1;
-        uint64_t h = jMix(kmer) & mask;
-        bool done = false;
-        for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
-            unsigned long long cur = key[h];
-            if (cur == 0) {
-                cur = atomicCAS(&key[h], 0ull, want);
-                if (cur == 0) { mine++; cur = want; }
-            }
-            if (cur == want) {
-                if ((val[h] & bits) != bits) atomicOr(&val[h], bits);
-                done = true;
-                break;
-            }
-            if ((probes & 255) == 255 && __hip_atomic_load(&st->full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        }
-        if (!done) { atomicOr(&st->full, 1u); stop = true; }
-    }
-    if (mine) atomicAdd(&claimed, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && claimed) {
-        const unsigned long long u = atomicAdd(&st->used, (unsigned long long)claimed) + claimed;
-        if (u * 10 > (mask + 1) * 9) atomicOr(&st->full, 1u);
-    }
+    jInsertBody<J_MARKED>(codes, len, k, bitmap, key, val, mask, st, 1, 0);
 }
 
-// junctionClassify in front of the junction table: a window without a bit is W_NONE without a probe; a window with one is looked up
-// and casts the first-occurrence vote. The rest of the tile pipeline (junctionMarkFirst .. junctionEmit) runs unchanged behind it.
 __global__ __launch_bounds__(JT) void junctionClassifyMarked(const uint8_t* __restrict__ codes, uint64_t len, int k, const unsigned long long* __restrict__ bitmap,
                                                              const unsigned long long* __restrict__ key, uint32_t* val, uint64_t mask, uint64_t t0, uint32_t tileLen,
                                                              unsigned long long* wslot, JState* st)
 {
-    __shared__ uint8_t s[J_WPB + 40];
-    const uint32_t i0 = blockIdx.x * (uint32_t)J_WPB;
-    jLoadCodes(s, codes, len, t0 + i0, k);
-    __syncthreads();
-    for (int j = 0; j < J_RUN; j++) {
-        const int w = j * JT + threadIdx.x;
-        const uint32_t i = i0 + (uint32_t)w;
-        if (i >= tileLen) break;
-        const uint64_t g = t0 + i;
-        unsigned long long out = W_NONE;
-        uint64_t kmer; bool isFwd; uint32_t bits;
-        if ((bitmap[g >> 6] >> (g & 63)) & 1ull) {
-            bool found = false;
-            uint64_t h = 0;
-            if (jWindow(s + w, k, kmer, isFwd, bits)) {
-                const unsigned long long want = kmer + 1;
-                h = jMix(kmer) & mask;
-                for (uint64_t probes = 0; probes <= mask; probes++, h = (h + 1) & mask) {
-                    const unsigned long long cur = key[h];
-                    if (cur == want) { found = true; break; }
-                    if (cur == 0) break;
-                }
-            }
-            if (!found) atomicOr(&st->lost, 1u);
-            else {
-                const uint32_t v = val[h], vote = V_PEND | (V_IDX - i);
-                if (v & V_ID) {}
-                else if (v & V_PEND) { if (v < vote) atomicMax(&val[h], vote); }
-                else atomicMax(&val[h], vote);      // (every key of this table is a junction: its value carries 0x100)
-                out = h | (isFwd ? W_FWD : 0ull);
-            }
-        }
-        wslot[i] = out;
-    }
+    jClassifyBody<true>(codes, len, k, bitmap, key, val, mask, t0, tileLen, wslot, st);
 }
 
 }  // namespace lcb_junction

@@ -1,70 +1,23 @@
 // tests/emu/junction_emu.cpp — TEST-ONLY: the kernels of the GPU junction finder (sibeliaz_amd/csrc/lcb_junction_kernels.h, unmodified) on the
 // lockstep wavefront emulator, driven like csrc/junctions.hip drives them (table regrowth, tiles in file order), writing the junction
 // file: junction_emu <k> <table_log2> <tile_windows> <out> <fasta...>. tests/test_junctions_emu.py compares it with lcb-mkgraph's.
-#include <hip/hip_runtime.h>     // the shadow header of this directory
-
-// what these kernels use beyond the block finder's kernels
-#include <algorithm>
-using std::min;
-static inline uint32_t emu_shfl_up(uint32_t v, int d, const char* f, int l) {
-    int lane = emu_thread_idx().x & 63; int src = lane >= d ? lane - d : lane;
-    return (uint32_t)emu_collective(EMU_SHFL, (uint64_t)v, src, f, l);
-}
-#define __shfl_up(v, d) emu_shfl_up((v), (d), __FILE__, __LINE__)
-static inline int emu_sync_count(int p) {
-    static thread_local int cnt;
-    if (emu_thread_idx().x == 0) cnt = 0;
-    __syncthreads(); if (p) cnt++; __syncthreads(); int r = cnt; __syncthreads(); return r;
-}
-#define __syncthreads_count(p) emu_sync_count((p) ? 1 : 0)
-static inline unsigned long long atomicCAS(unsigned long long* a, unsigned long long cmp, unsigned long long val) { unsigned long long old = *a; if (old == cmp) *a = val; return old; }
-static inline int __popc(uint32_t x) { return __builtin_popcount(x); }
-
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "emu_runtime.h"
-#include "lcb_fasta.h"
-#include "lcb_junction_kernels.h"
-using namespace lcb_junction;
-template <class F> void launch(uint32_t grid, int threads, F body) { for (uint32_t b = 0; b < grid; b++) emu_run_block(b, threads / 64, body); }
+#include "junction_emu_common.h"
 int main(int argc, char** argv) {
     int k = atoi(argv[1]); uint32_t capLog2 = atoi(argv[2]); uint32_t tileWindows = atoi(argv[3]); std::string out = argv[4];
-    std::vector<lcb_fasta::Record> rec;
-    for (int i = 5; i < argc; i++) lcb_fasta::readFasta(argv[i], rec);
-    std::vector<uint64_t> base(rec.size() + 1), recLen(rec.size());
-    uint64_t len = 1;
-    for (size_t r = 0; r < rec.size(); r++) { base[r] = len; len += rec[r].seq.size() + 1; recLen[r] = rec[r].seq.size(); }
-    std::vector<uint8_t> codes(len, 4);
-    for (size_t r = 0; r < rec.size(); r++) for (size_t i = 0; i < rec[r].seq.size(); i++) { int c = lcb_fasta::code(rec[r].seq[i]); codes[base[r] + i] = c < 0 ? 4 : c; }
+    const Input in(argv + 5, argv + argc);
+    const uint64_t len = in.len;
     std::vector<unsigned long long> key; std::vector<uint32_t> val; JState st; uint64_t mask; int rebuilds = 0;
     for (;; capLog2++) {
         uint64_t cap = 1ull << capLog2; mask = cap - 1; key.assign(cap, 0); val.assign(cap, 0); memset(&st, 0, sizeof(st));
         uint32_t grid = (len + J_WPB - 1) / J_WPB;
-        launch(grid, JT, [&]() { junctionInsert(codes.data(), len, k, key.data(), val.data(), mask, &st); });
+        launch(grid, JT, [&]() { junctionInsert(in.codes.data(), len, k, key.data(), val.data(), mask, &st); });
         if (!st.full && st.used * 10 <= cap * 9) break;
         rebuilds++;
     }
-    uint32_t tileBuf = std::min<uint64_t>(tileWindows, len);
-    std::vector<unsigned long long> wslot(tileBuf); std::vector<JRecord> o(tileBuf); std::vector<uint32_t> cj((tileBuf + JT - 1) / JT), cf((tileBuf + JT - 1) / JT);
-    FILE* f = fopen(out.c_str(), "wb"); size_t curRec = 0; uint64_t occ = 0; int tiles = 0;
-    auto put = [&](uint32_t pos, int64_t id) { fwrite(&pos, 4, 1, f); fwrite(&id, 8, 1, f); };
-    for (uint64_t t0 = 0; t0 < len; t0 += tileWindows, tiles++) {
-        uint32_t tileLen = std::min<uint64_t>(tileWindows, len - t0), nb = (tileLen + JT - 1) / JT;
-        launch((tileLen + J_WPB - 1) / J_WPB, JT, [&]() { junctionClassify(codes.data(), len, k, key.data(), val.data(), mask, t0, tileLen, wslot.data(), &st); });
-        launch(nb, JT, [&]() { junctionMarkFirst(wslot.data(), val.data(), tileLen, cj.data(), cf.data()); });
-        launch(1, 1024, [&]() { junctionScan(cj.data(), cf.data(), nb, &st); });
-        launch(nb, JT, [&]() { junctionAssignIds(wslot.data(), val.data(), tileLen, cf.data(), &st); });
-        launch(nb, JT, [&]() { junctionEmit(wslot.data(), val.data(), tileLen, cj.data(), t0, o.data()); });
-        if (st.lost) { fprintf(stderr, "LOST\n"); return 1; }
-        for (uint64_t q = 0; q < st.totJ; q++) {
-            while (o[q].g >= base[curRec] + recLen[curRec]) { put(0xFFFFFFFFu, INT64_MAX); curRec++; }
-            put((uint32_t)(o[q].g - base[curRec]), o[q].id);
-        }
-        occ += st.totJ;
-    }
-    for (; curRec < recLen.size(); curRec++) put(0xFFFFFFFFu, INT64_MAX);
+    FILE* f = fopen(out.c_str(), "wb"); uint64_t occ = 0; int tiles = 0;
+    if (!runTiles(in, tileWindows, f, val.data(), st, occ, tiles, [&](uint64_t t0, uint32_t tileLen, unsigned long long* wslot) {
+            junctionClassify(in.codes.data(), len, k, key.data(), val.data(), mask, t0, tileLen, wslot, &st);
+        })) { fprintf(stderr, "LOST\n"); return 1; }
     fclose(f);
-    fprintf(stderr, "emu: %zu records, %llu occ, %llu ids, slots 2^%u, rebuilds %d, tiles %d\n", rec.size(), (unsigned long long)occ, st.idNext, capLog2, rebuilds, tiles);
+    fprintf(stderr, "emu: %zu records, %llu occ, %llu ids, slots 2^%u, rebuilds %d, tiles %d\n", in.recLen.size(), (unsigned long long)occ, st.idNext, capLog2, rebuilds, tiles);
 }
