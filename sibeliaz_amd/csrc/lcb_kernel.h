@@ -322,6 +322,8 @@ struct LcbStateT {
     uint32_t* vNClaimed;       // LDS counter: number of them
     uint32_t* vTicket;         // LDS counter: next entry of the touch list to hand to a wavefront (votes shared by more than two wavefronts)
     uint32_t* vOvf;            // LDS flag: a walk of the current vote could not place a vertex
+    uint32_t* vRec;            // LDS: voter records of a resolved vote, 4 words each (lcb_vote_resolve) ...
+    uint32_t* vItem;           // ... and its items
     uint32_t voteCap, voteShift;
     uint32_t* scr;             // LDS scratch, 4 * 64 words
     uint32_t* bloom;           // LDS Bloom filter over the path vertex set
@@ -1065,6 +1067,265 @@ __device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool use
     }
 }
 
+// Stage A of lcb_vote_walk as two functions, for the resolved heavy vote of the wide and big variants below (lcb_vote_resolve). The
+// compact walk keeps its own inlined copy: calling these from it moved the register allocation of the compact kernels (SGPR spills
+// 292 -> 266 / 402 -> 421, a compact vote +1 % in the instrumented pass), and the k = 25 shapes run almost entirely there.
+// First half, the requests. Entry t of the touch list: its instance fields, its window word and the eight bitmap words its window
+// can cover, all requested together (nothing is consumed here).
+template <class F> struct LcbVoterReq {
+    bool isV, walks, scan, positive, up;
+    uint32_t vI, vE, g0, rem, weight, fl, win;
+    F fb;                                                          // flat bit of step 1 (scan)
+    uint32_t uw0, uw1, uw2, uw3, uw4, uw5, uw6, uw7;
+};
+template <class ST>
+__device__ __forceinline__ LcbVoterReq<typename ST::Flat> lcb_voter_request(const ST& S, uint32_t t, uint32_t nTouch, bool forward, bool tryUsed, bool useGood, uint32_t maxW)
+{
+    const LcbTables& T = S.T;
+    typedef typename ST::Flat Flat;
+    LcbVoterReq<Flat> R;
+    R.isV = false;
+    R.vI = 0; R.vE = 0; R.g0 = 0; R.rem = 0; R.weight = 0; R.fl = 0;
+    if (t < nTouch) {
+        R.vI = S.touch[t];
+        R.vE = useGood ? (uint32_t)S.goodPos[R.vI] : R.vI;          // position in the voting list (its order breaks ties)
+        R.isV = R.vE != ST::NONE;
+    }
+    if (R.isV) {
+        R.fl = S.iFlags[R.vI];
+        const uint32_t fp = S.iFrontPos[R.vI], bp = S.iBackPos[R.vI];
+        R.g0 = forward ? S.iBackG[R.vI] : S.iFrontG[R.vI];
+        const uint32_t lo = S.iLo[R.vI], hi = S.iHi[R.vI];
+        R.weight = lcb_absdiff(fp, bp) + 1u;                    // blocksfinder.h:719
+        R.rem = (forward == ((R.fl & LCB_FLAG_POS) != 0)) ? hi - 1u - R.g0 : R.g0 - lo;   // steps for which it.Valid() holds
+    }
+    R.positive = (R.fl & LCB_FLAG_POS) != 0; R.up = forward == R.positive;
+    Flat sb = 0;
+    if (ST::SEG) sb = (Flat)S.segBase[lcb_fl_seg(R.fl)];
+    const Flat f0 = sb + R.g0;
+    R.walks = R.isV && R.rem != 0;
+    R.win = 0;
+    if (R.walks) R.win = T.posWin[f0];
+    // IsUsed of step d: + strand bit g, - strand bit g - 1 (none at the chromosome start). The bits of steps 1, 2, ... in walking
+    // order: flat bit fb, then fb + 1, ... (up) or fb - 1, ... (down); 8 words of it cover at least 225 steps.
+    const uint32_t delta = R.positive ? 0u : 1u;
+    R.scan = R.walks && !tryUsed && !(!R.up && f0 < (Flat)(1u + delta));   // (down from flat position 0 / 1 on the - strand: no step has a bit)
+    R.fb = R.scan ? (R.up ? f0 + 1u - delta : f0 - 1u - delta) : (Flat)0;
+    R.uw0 = 0; R.uw1 = 0; R.uw2 = 0; R.uw3 = 0; R.uw4 = 0; R.uw5 = 0; R.uw6 = 0; R.uw7 = 0;
+    if (R.scan) {
+        const uint32_t W0 = (uint32_t)(R.fb >> 5);
+        const uint32_t um = R.up ? 0xFFFFFFFFu : 0u;       // (selects by mask, not by branch: the eight addresses are straight-line code)
+#define LCB_WIDX(k) ((((W0 + (k)) < maxW ? (W0 + (k)) : maxW) & um) | ((W0 - (W0 < (k) ? W0 : (k))) & ~um))
+        uint32_t a0 = LCB_WIDX(0u), a1 = LCB_WIDX(1u), a2 = LCB_WIDX(2u), a3 = LCB_WIDX(3u), a4 = LCB_WIDX(4u), a5 = LCB_WIDX(5u), a6 = LCB_WIDX(6u), a7 = LCB_WIDX(7u);
+#undef LCB_WIDX
+        if (S.U.tab) {
+            const auto tab = LCB_GLOBAL_U32(S.U.tab);
+            const uint32_t o0 = tab[a0 >> LCB_PAGE_SHIFT], o1 = tab[a1 >> LCB_PAGE_SHIFT], o2 = tab[a2 >> LCB_PAGE_SHIFT], o3 = tab[a3 >> LCB_PAGE_SHIFT];
+            const uint32_t o4 = tab[a4 >> LCB_PAGE_SHIFT], o5 = tab[a5 >> LCB_PAGE_SHIFT], o6 = tab[a6 >> LCB_PAGE_SHIFT], o7 = tab[a7 >> LCB_PAGE_SHIFT];
+            a0 += o0; a1 += o1; a2 += o2; a3 += o3; a4 += o4; a5 += o5; a6 += o6; a7 += o7;
+        }
+        R.uw0 = S.U.live[a0]; R.uw1 = S.U.live[a1]; R.uw2 = S.U.live[a2]; R.uw3 = S.U.live[a3];
+        R.uw4 = S.U.live[a4]; R.uw5 = S.U.live[a5]; R.uw6 = S.U.live[a6]; R.uw7 = S.U.live[a7];
+    }
+    return R;
+}
+
+// Stage A, second half: the contributing steps nv of the voter (brk: a breaking step - a used position - follows them), its footprint
+// and the event counter.
+template <bool STATS, class ST>
+__device__ __forceinline__ void lcb_voter_resolve(ST& S, LcbVoterReq<typename ST::Flat>& R, uint32_t dm, bool tryUsed, uint32_t& nv, uint32_t& brk)
+{
+    typedef typename ST::Flat Flat;
+    nv = 0; brk = 0;                                           // steps that vote; 1 if a breaking step (used / in the path) follows them
+    if (R.walks) {
+        const uint32_t wv = R.up ? (R.win & 0xFFFFu) : (R.win >> 16);
+        uint32_t L = wv > dm ? wv : dm;
+        if (L > R.rem) L = R.rem;
+        nv = L;
+        if (R.scan) {
+            const bool up = R.up;
+            const Flat fb = R.fb;
+            uint32_t uw0 = R.uw0, uw1 = R.uw1, uw2 = R.uw2, uw3 = R.uw3, uw4 = R.uw4, uw5 = R.uw5, uw6 = R.uw6, uw7 = R.uw7;
+            const uint32_t Lu = (!R.positive && !up && L == R.rem) ? L - 1u : L;   // the step onto the chromosome's first position reads no bit on the - strand
+            const uint32_t sh = up ? ((uint32_t)fb & 31u) : 31u - ((uint32_t)fb & 31u);
+            if (!up) { uw0 = LCB_BREV32(uw0); uw1 = LCB_BREV32(uw1); uw2 = LCB_BREV32(uw2); uw3 = LCB_BREV32(uw3); uw4 = LCB_BREV32(uw4); uw5 = LCB_BREV32(uw5); uw6 = LCB_BREV32(uw6); uw7 = LCB_BREV32(uw7); }
+            const uint64_t s0 = (uint64_t)uw0 | ((uint64_t)uw1 << 32), s1 = (uint64_t)uw2 | ((uint64_t)uw3 << 32), s2 = (uint64_t)uw4 | ((uint64_t)uw5 << 32), s3 = (uint64_t)uw6 | ((uint64_t)uw7 << 32);
+            const uint64_t x0 = (s0 >> sh) | ((s1 << 1) << (63u - sh)), x1 = (s1 >> sh) | ((s2 << 1) << (63u - sh)), x2 = (s2 >> sh) | ((s3 << 1) << (63u - sh)), x3 = s3 >> sh;
+            const uint32_t have = 256u - sh;                   // steps whose bit is in x0 .. x3
+            const uint32_t n = Lu < have ? Lu : have;
+            uint32_t first = 0;                                // first used step (1-based), 0 = none
+#define LCB_SCAN64(x, base) if (!first && n > (base)) { const uint32_t c_ = n - (base) < 64u ? n - (base) : 64u; const uint64_t m_ = (x) & (c_ == 64u ? ~0ull : ((1ull << c_) - 1ull)); if (m_) first = (base) + (uint32_t)__ffsll((long long)m_); }
+            LCB_SCAN64(x0, 0u) LCB_SCAN64(x1, 64u) LCB_SCAN64(x2, 128u) LCB_SCAN64(x3, 192u)
+#undef LCB_SCAN64
+            for (uint32_t d = have + 1; !first && d <= Lu; d++)    // (windows of more than 225 steps: -b beyond 225)
+                if (lcb_used_bit(S.U, (Flat)(up ? fb + (d - 1u) : fb - (d - 1u)))) first = d;
+            if (first) { nv = first - 1u; brk = 1u; }
+        }
+    }
+    if (R.isV && !tryUsed) {
+        // steps 1 .. nv read used == 0 (the read-out widens by one position for the - strand's bit g - 1)
+        const uint32_t ge = R.up ? R.g0 + nv : R.g0 - nv;
+        const uint32_t fs = lcb_fp_slot(S, R.vI);
+        atomicMin(&S.fpLo[fs], ge);
+        atomicMax(&S.fpHi[fs], ge);
+    }
+    if (STATS && R.isV) S.cWalk += nv + brk;                      // loop iterations entered: contributing steps plus the breaking one
+}
+
+// ---- The heavy vote of the 16-wavefront variants: wave 0 resolves the voters BEFORE it wakes the helpers, everybody deals items.
+// With tickets over the touch list (lcb_vote_walk_v1) every chunk of a window is its own round trip: fields of the voter, then
+// posPos / posId / the `used` word of 64 steps, consumed before the next chunk is requested - 0.9-1.0 us per chunk, 70-93 chunks in a
+// config-3 vote of 30-37 voters (profiles/r06). Here wave 0 runs stage A of the compact walk over the whole touch list (lanes =
+// entries, one round trip for all voters) while the helpers still sleep at barrier A, and leaves in LDS
+//   a record per walking voter: g0, nv | strand << 16 | segment << 17, weight, position in the voting list;
+//   a flat list of items (voter record | chunk << 16), ceil(nv / 64) per voter, laid out by a prefix sum over the lanes.
+// After barrier A every wavefront draws LCB_VB items at a time from the ticket counter; an item is ONE load per lane (the id of step
+// chunk * 64 + lane + 1 <= nv) and the hash insert. No barrier is added, and no item touches another wavefront's voter: the pass
+// walks WITHOUT path stops and is verified afterwards (lcb_vote_any_in_path; the wide variant's path set is in LDS), and a hit or
+// an overflow repeats the vote with exact = true, i.e. with lcb_vote_walk_v1, as the variants behind a Bloom filter always did.
+// Which variants: bit m of LCB_VOTE_RESOLVE_MODES (wide and big only - the compact variant has its own walk, the huge one keeps v1);
+// which votes: LCB_VOTE_RESOLVE_MIN <= voters <= LCB_VOTE_RESOLVE_MAX in workgroups of more than two wavefronts. The k = 25 shapes
+// (14 voters of one chunk each) stay below the minimum: resolving first is a loss there (profiles/r06).
+#ifndef LCB_VOTE_RESOLVE_MODES
+#define LCB_VOTE_RESOLVE_MODES 0x6u
+#endif
+#ifndef LCB_VOTE_RESOLVE_MIN
+#define LCB_VOTE_RESOLVE_MIN 24u       // = LCB_VOTE_SHARE_MIN: exactly the votes that share the reduction
+#endif
+#ifndef LCB_VOTE_RESOLVE_MAX
+#define LCB_VOTE_RESOLVE_MAX 256u      // records in LDS (16 B each); more than any config-3 vote has
+#endif
+#ifndef LCB_VOTE_RESOLVE_ITEMS
+#define LCB_VOTE_RESOLVE_ITEMS 2048u   // items in LDS (4 B each); a vote with more runs today's walk
+#endif
+#define LCB_VOTE_RESOLVE_OF(MODE, NW) ((NW) > 2 && ((MODE) == 1 || (MODE) == 2) && (((LCB_VOTE_RESOLVE_MODES) >> (MODE)) & 1u) != 0)
+static_assert(LCB_VOTE_RESOLVE_MIN >= 2u && LCB_VOTE_RESOLVE_MAX <= 65536u, "a resolved vote wakes the helpers; a record index has 16 bits");
+// (emulator tests only, -DLCB_TEST_RESOLVE_EVENT=<function>: what the resolved votes of an input went through)
+enum { LCB_RV_RESOLVED = 0, LCB_RV_CHUNK1, LCB_RV_USED_BEYOND_64, LCB_RV_REPEAT_HIT, LCB_RV_ABOVE_MAX, LCB_RV_ITEMS_FULL, LCB_RV_ROUND2, LCB_RV_COUNT };
+#ifdef LCB_TEST_RESOLVE_EVENT
+void LCB_TEST_RESOLVE_EVENT(int what);
+#define LCB_RESOLVE_EVENT_IF(cond, what) do { if (cond) LCB_TEST_RESOLVE_EVENT(what); } while (0)
+#else
+#define LCB_RESOLVE_EVENT_IF(cond, what) ((void)0)
+#endif
+#define LCB_RESOLVE_EVENT(S, what) LCB_RESOLVE_EVENT_IF((S).lane == 0, what)
+
+// Does the vote over the current touch list take the resolved path? (wave 0; the helpers read the answer from LCB_MAIL_FLAGS)
+template <int NW, class ST>
+__device__ __forceinline__ bool lcb_vote_resolves(const ST& S)
+{
+    return LCB_VOTE_RESOLVE_OF(ST::MODE, NW) && S.nTouch >= LCB_VOTE_RESOLVE_MIN && S.nTouch <= LCB_VOTE_RESOLVE_MAX;
+}
+
+// Inclusive prefix sum over the lanes (the DPP ladder of lcb_wave_umax; every lane gets its own sum).
+__device__ __forceinline__ uint32_t lcb_wave_scan(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31
+    return v;
+}
+
+// Wave 0, before barrier A: stage A over the whole touch list (lanes = entries, 64 per round), records and items into LDS.
+// Returns the number of items, or ~0u if the item list cannot hold them (nothing of the vote table has been touched then; the
+// footprints stay, a superset; the caller puts the event counter back).
+template <bool STATS, bool PROF, class ST>
+__device__ inline uint32_t lcb_vote_resolve(ST& S, bool forward, bool tryUsed, bool useGood)
+{
+    typedef typename ST::Flat Flat;
+    const uint32_t depth = (uint32_t)S.P.depth;
+    const uint32_t dm = depth ? depth - 1u : 0u;                  // steps allowed by `step < lookingDepth` alone
+    const uint32_t nTouch = S.nTouch;
+    const uint32_t maxW = (uint32_t)(S.T.nPos >> 5);             // (the bitmap has at least nPos / 32 + 2 words)
+    uint32_t nRec = 0, nItems = 0;
+    for (uint32_t p0 = 0; p0 < nTouch; p0 += 64) {
+        LCB_NO_LOADS_IN_FLIGHT();                                  // (see lcb_vote_walk)
+        LcbVoterReq<Flat> R = lcb_voter_request(S, p0 + S.lane, nTouch, forward, tryUsed, useGood, maxW);
+        uint32_t nv, brk;
+        lcb_voter_resolve<STATS>(S, R, dm, tryUsed, nv, brk);
+        if (PROF) S.pfVoters += (uint32_t)__popcll(__ballot(R.walks));
+        LCB_RESOLVE_EVENT_IF(brk && nv >= 64u, LCB_RV_USED_BEYOND_64);
+        const bool has = nv != 0;
+        const unsigned long long hasM = __ballot(has);
+        const uint32_t nch = (nv + 63u) >> 6;                      // items of this voter
+        const uint32_t incl = lcb_wave_scan(nch);
+        const uint32_t total = lcb_rl(incl, 63);
+        if (nItems + total > LCB_VOTE_RESOLVE_ITEMS) return ~0u;
+        if (has) {
+            const uint32_t r = nRec + (uint32_t)__popcll(hasM & ((1ull << S.lane) - 1));
+            uint32_t* rec = S.vRec + 4u * r;
+            rec[0] = R.g0; rec[1] = nv | (R.positive ? 0x10000u : 0u) | (lcb_fl_seg(R.fl) << 17); rec[2] = R.weight; rec[3] = R.vE;
+            uint32_t* it = S.vItem + nItems + (incl - nch);
+            for (uint32_t c = 0; c < nch; c++) it[c] = r | (c << 16);
+        }
+        nRec += (uint32_t)__popcll(hasM); nItems += total;
+    }
+    return nItems;
+}
+
+// Every wavefront, after barrier A: items of the resolved vote into the vote table, LCB_VB per draw - their id loads are issued back
+// to back before the first is consumed. An item reads nothing but the ids of its steps.
+template <bool PROF, class ST>
+__device__ inline void lcb_vote_items(ST& S, bool forward, uint32_t nItems)
+{
+    const LcbTables& T = S.T;
+    typedef typename ST::Flat Flat;
+    const uint32_t vmask = S.voteCap - 1;
+    const uint32_t claimCap = S.voteCap - (S.voteCap >> 2);
+    for (;;) {
+        uint32_t t = 0;
+        if (S.lane == 0) t = atomicAdd(S.vTicket, (uint32_t)LCB_VB);
+        t = lcb_rfl(t);
+        if (t >= nItems) break;
+        uint32_t itF[LCB_VB], itC[LCB_VB];                         // the item's voter record, one word per lane (lanes 0..3); its chunk
+        int32_t itId[LCB_VB];
+#pragma unroll
+        for (int q = 0; q < LCB_VB; q++) {
+            itF[q] = 0; itC[q] = 0; itId[q] = 0;
+            if (t + q < nItems) {
+                const uint32_t it = lcb_rfl(S.vItem[t + q]);
+                itC[q] = it >> 16;
+                if (S.lane < 4u) itF[q] = S.vRec[4u * (it & 0xFFFFu) + S.lane];
+                const uint32_t g0 = lcb_rl(itF[q], 0), w1 = lcb_rl(itF[q], 1);
+                const bool up = forward == ((w1 & 0x10000u) != 0);
+                const uint32_t d = itC[q] * 64 + S.lane + 1;
+                const Flat sb = ST::SEG ? (Flat)lcb_rfl(S.segBase[w1 >> 17]) : (Flat)0;
+                if (d <= (w1 & 0xFFFFu)) itId[q] = (T.posId + sb)[up ? g0 + d : g0 - d];   // (wave-uniform table base + 32-bit lane offset)
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < LCB_VB; q++) {
+            if (t + q < nItems) {
+                if (PROF) S.pfChunks++;
+                if (itC[q]) LCB_RESOLVE_EVENT(S, LCB_RV_CHUNK1);
+                const uint32_t w1 = lcb_rl(itF[q], 1), wgt = lcb_rl(itF[q], 2), e = lcb_rl(itF[q], 3);
+                const uint32_t d = itC[q] * 64 + S.lane + 1;
+                const int32_t vid = (w1 & 0x10000u) ? itId[q] : -itId[q];
+                if (d <= (w1 & 0xFFFFu)) {
+                    uint32_t h = lcb_hash(vid, S.voteShift);
+                    int32_t old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
+                    uint32_t probe = 0;
+                    while (old != LCB_EMPTY_KEY && old != vid && probe < S.voteCap) {
+                        h = (h + 1) & vmask; probe++;
+                        old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
+                    }
+                    if (old == LCB_EMPTY_KEY) {
+                        const uint32_t tt = atomicAdd(S.vNClaimed, 1u);
+                        if (tt < claimCap) S.vTouched[tt] = (typename ST::Idx)h; else *S.vOvf = 1u;
+                    }
+                    if (old == LCB_EMPTY_KEY || old == vid) {
+                        atomicAdd(&S.vCount[h], wgt);
+                        atomicMax(&S.vLast[h], ((typename ST::VLast)e << ST::LAST_SHIFT) | d);
+                    } else *S.vOvf = 1u;
+                }
+            }
+        }
+    }
+}
+
 // Is one of the vertices named by the entries [s0, s1) of the touched list of the vote table in the path? (after a pass with
 // exact = false, see lcb_vote_walk; wave-uniform result)
 template <class ST>
@@ -1114,7 +1375,7 @@ __device__ inline LcbBest lcb_vote_argmax(const ST& S, bool forward, bool useGoo
 }
 
 // Mailbox words through which wave 0 hands a vote to the helper wavefronts of its workgroup.
-enum { LCB_MAIL_CMD = 0, LCB_MAIL_FLAGS, LCB_MAIL_NLIST, LCB_MAIL_FLANK, LCB_MAIL_NTOUCH, LCB_MAIL_FPSPLIT, LCB_MAIL_FPSHIFT, LCB_MAIL_WORDS = 8 };
+enum { LCB_MAIL_CMD = 0, LCB_MAIL_FLAGS, LCB_MAIL_NLIST, LCB_MAIL_FLANK, LCB_MAIL_NTOUCH, LCB_MAIL_FPSPLIT, LCB_MAIL_FPSHIFT, LCB_MAIL_NITEMS, LCB_MAIL_WORDS = 8 };
 enum { LCB_CMD_VOTE = 1, LCB_CMD_EXIT = 2 };
 
 // Clears the vote-table slots named by the entries [s0, s1) of the touched list (blocksfinder.h:761-766).
@@ -1161,24 +1422,41 @@ __device__ inline LcbBest lcb_vote_pass(ST& S, bool forward, bool tryUsed, bool 
     hit = false;
     const bool multi = NW > 1 && S.nTouch > 1;                     // the helper wavefronts take part
     const bool share = multi && S.nTouch >= LCB_VOTE_SHARE_MIN;    // ... also in the reduction and the clearing
+    // a heavy vote of the 16-wavefront variants: wave 0 resolves the voters while the helpers still sleep at barrier A
+    bool resolve = !exact && lcb_vote_resolves<NW>(S);
+    uint32_t nItems = 0;
+    uint64_t tResolve = 0;
+    if (LCB_VOTE_RESOLVE_OF(ST::MODE, NW) && resolve) {
+        const uint64_t tr0 = PROF ? wall_clock64() : 0;
+        const uint64_t cWalk0 = S.cWalk;
+        nItems = lcb_vote_resolve<STATS, PROF>(S, forward, tryUsed, useGood);
+        if (nItems == ~0u) {                                       // more items than the list holds: today's walk, verified afterwards
+            resolve = false; nItems = 0;
+            if (STATS) S.cWalk = cWalk0;
+            LCB_RESOLVE_EVENT(S, LCB_RV_ITEMS_FULL);
+        } else { LCB_RESOLVE_EVENT(S, LCB_RV_RESOLVED); LCB_RESOLVE_EVENT_IF(S.lane == 0 && S.nTouch > 64u, LCB_RV_ROUND2); }
+        if (PROF) tResolve = wall_clock64() - tr0;
+    }
     if (multi) {
         // wake the helper wavefronts: every wave walks its share of the voters
         if (S.lane == 0) {
-            S.mail[LCB_MAIL_FLAGS] = (forward ? 1u : 0u) | (tryUsed ? 2u : 0u) | (useGood ? 4u : 0u) | (share ? 8u : 0u) | (exact ? 16u : 0u);
+            S.mail[LCB_MAIL_FLAGS] = (forward ? 1u : 0u) | (tryUsed ? 2u : 0u) | (useGood ? 4u : 0u) | (share ? 8u : 0u) | (exact ? 16u : 0u) | (resolve ? 32u : 0u);
             S.mail[LCB_MAIL_NTOUCH] = S.nTouch;
             S.mail[LCB_MAIL_FPSPLIT] = S.fpSplit; S.mail[LCB_MAIL_FPSHIFT] = S.fpShift;
-            if (!LCB_WALK_V2_OF(ST)) *S.vTicket = 0;
+            S.mail[LCB_MAIL_NITEMS] = nItems;
+            if (!LCB_WALK_V2_OF(ST) || resolve) *S.vTicket = 0;
             S.mail[LCB_MAIL_CMD] = LCB_CMD_VOTE;
         }
         __syncthreads();                                           // A
     }
     const uint64_t tw0 = PROF ? wall_clock64() : 0;
-    lcb_vote_walk<STATS, PROF>(S, forward, tryUsed, useGood, 0, multi ? (uint32_t)NW : 1u, exact);
+    if (LCB_VOTE_RESOLVE_OF(ST::MODE, NW) && resolve) lcb_vote_items<PROF>(S, forward, nItems);
+    else lcb_vote_walk<STATS, PROF>(S, forward, tryUsed, useGood, 0, multi ? (uint32_t)NW : 1u, exact);
     const uint64_t tw1 = PROF ? wall_clock64() : 0;
     if (multi) __syncthreads();                                    // B: all walks done
     else LCB_SYNC_IF(LcbCfg<ST::MODE>::IDX_LDS);
     const uint64_t tw2 = PROF ? wall_clock64() : 0;
-    if (PROF && !LCB_PROF_PUSH) { S.pfTWalk += tw1 - tw0; S.pfTWaitB += tw2 - tw1; }
+    if (PROF && !LCB_PROF_PUSH) { S.pfTWalk += tw1 - tw0 + tResolve; S.pfTWaitB += tw2 - tw1; }
     uint32_t nTouched = lcb_rfl(*S.vNClaimed);
     if (nTouched > claimCap) nTouched = claimCap;
     if (STATS && multi && S.lane == 0) { S.cWalk += *S.mailWalk; *S.mailWalk = 0; }
@@ -1240,9 +1518,13 @@ __device__ inline int32_t lcb_vote(ST& S, bool forward, uint32_t attempts, uint3
         bool ovfAny = false, hit = false;
         if (PROF) S.pfTouchSum += S.nTouch;
         LcbBest b;
+        // (a resolved vote walks its first pass without path stops in every variant, lcb_vote_resolve)
+        const bool defer = DEFER || lcb_vote_resolves<NW>(S);
+        LCB_RESOLVE_EVENT_IF(S.lane == 0 && LCB_VOTE_RESOLVE_OF(ST::MODE, NW) && S.nTouch > LCB_VOTE_RESOLVE_MAX, LCB_RV_ABOVE_MAX);
         for (uint32_t pass = 0;; pass++) {
-            b = lcb_vote_pass<STATS, NW, PROF>(S, forward, tryUsed, useGood, pass != 0 || !DEFER, ovfAny, hit);
-            if (pass != 0 || !DEFER || !(hit || ovfAny)) break;
+            b = lcb_vote_pass<STATS, NW, PROF>(S, forward, tryUsed, useGood, pass != 0 || !defer, ovfAny, hit);
+            if (pass != 0 || !defer || !(hit || ovfAny)) break;
+            LCB_RESOLVE_EVENT_IF(S.lane == 0 && hit && lcb_vote_resolves<NW>(S), LCB_RV_REPEAT_HIT);
             // a touched vertex is in the path (or the table overflowed, so that the touched list is incomplete - a pass with path stops
             // may touch fewer vertices): the vote as the reference walks it. After an overflow the table may hold stale keys.
             if (ovfAny) {
@@ -1937,6 +2219,9 @@ __device__ inline void lcb_process_body(const LcbTables& T, const LcbKParams& P,
     __shared__ uint32_t sSegFirst[SEG ? LCB_MAX_SEG + 2 : 1];
     __shared__ uint8_t sFpSeg[(SEG && INST_LDS) ? IC : 1];
     __shared__ uint32_t sMisc[4];
+    constexpr bool RESOLVE = LCB_VOTE_RESOLVE_OF(MODE, NW);
+    __shared__ uint32_t sVRec[RESOLVE ? 4 * LCB_VOTE_RESOLVE_MAX : 1];
+    __shared__ uint32_t sVItem[RESOLVE ? LCB_VOTE_RESOLVE_ITEMS : 1];
     __shared__ uint32_t sMail[LCB_MAIL_WORDS];
     __shared__ uint32_t sPart[8 * NW];
     __shared__ unsigned long long sMailWalk[1];
@@ -1998,6 +2283,7 @@ __device__ inline void lcb_process_body(const LcbTables& T, const LcbKParams& P,
     S.iBackDist = (int32_t*)(instBase + 8 * instStride);
     S.scr = sScr; S.vNClaimed = &sMisc[0]; S.vOvf = &sMisc[1]; S.vTicket = &sMisc[2];
     S.mail = sMail; S.mailWalk = sMailWalk; S.part = sPart;
+    if (RESOLVE) { S.vRec = sVRec; S.vItem = sVItem; } else { S.vRec = nullptr; S.vItem = nullptr; }
     const uint32_t waveId = lcb_rfl(threadIdx.x >> 6);
     S.dbg = (W.dbg && waveId == 0) ? W.dbg + 16u * blockIdx.x : nullptr;
     S.abort = W.abort;
@@ -2022,7 +2308,8 @@ __device__ inline void lcb_process_body(const LcbTables& T, const LcbKParams& P,
                 S.nTouch = lcb_rfl(S.mail[LCB_MAIL_NTOUCH]);
                 S.fpSplit = lcb_rfl(S.mail[LCB_MAIL_FPSPLIT]); S.fpShift = lcb_rfl(S.mail[LCB_MAIL_FPSHIFT]);
                 S.cWalk = 0;
-                lcb_vote_walk<STATS>(S, (flags & 1u) != 0, (flags & 2u) != 0, (flags & 4u) != 0, waveId, NW, (flags & 16u) != 0);
+                if (RESOLVE && (flags & 32u)) lcb_vote_items<false>(S, (flags & 1u) != 0, lcb_rfl(S.mail[LCB_MAIL_NITEMS]));   // a resolved vote: items, not voters
+                else lcb_vote_walk<STATS>(S, (flags & 1u) != 0, (flags & 2u) != 0, (flags & 4u) != 0, waveId, NW, (flags & 16u) != 0);
                 if (STATS) {
                     const unsigned long long w = (unsigned long long)lcb_wave_sum((int64_t)S.cWalk);
                     if (S.lane == 0 && w) atomicAdd(S.mailWalk, w);
