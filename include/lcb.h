@@ -254,6 +254,26 @@ int lcb_device_set_used(lcb_device* d, const uint32_t* words, int64_t n_words);
 /* 1: collect lcb_counters in the kernels (slower; used for the roofline's algorithmic bytes). */
 int lcb_device_set_stats_mode(lcb_device* d, int on);
 
+/* ---- seeds on the device: the enumeration and the sort of lcb_enumerate_seeds from the tables the device already holds (occurrence
+ * lists, occurrence records, characters), with HIP kernels: a counting pass, a scan, a writing pass, then a stable LSD radix sort over
+ * the key bytes (DESIGN.md has the kernels, the key layout and the memory formula). Device memory is taken for the call and released
+ * before it returns; a request that does not fit what the device reports free fails up front with both numbers in the message.
+ * Both calls run on the device's synchronous stream: like every call on an lcb_device they come from the device's one host thread and
+ * not while an lcb_find_blocks* runs on that device. */
+typedef struct {            /* output only; may be NULL */
+    int64_t seeds, vertices;        /* S; lists looked at */
+    int64_t max_count;              /* largest count */
+    int32_t sort_passes, sort_passes_skipped;
+    uint64_t device_bytes;          /* most device memory held by the call, by its own account */
+    double count_ms, fill_ms, sort_ms, copy_ms;   /* device phases hipEvent-timed; copy = D2H + expansion to lcb_seed */
+} lcb_seed_stats;
+/* lcb_enumerate_seeds on the device's own tables: same seeds, same order, *out malloc'ed (free with lcb_free; allocated even
+ * for 0 seeds, as lcb_enumerate_seeds does). -1 on error. Does not read or change the `used` state. */
+int64_t lcb_device_enumerate_seeds(lcb_device* d, lcb_seed** out, lcb_seed_stats* stats);
+/* Sort n caller-supplied seeds into processing order (Bundle::operator<) on the device, in place. Error if a count or a
+ * resolve_pos does not fit 32 bits or a resolve_chr 24. Seeds with equal keys keep their order. */
+int lcb_device_sort_seeds(lcb_device* d, lcb_seed* seeds, int64_t n);
+
 /* THE HOT PATH: ProcessVertex::Process (blocksfinder.h:228-310) for a batch of seeds, each against the
  * device's current `used` state, one seed per workgroup (wavefront 0 runs the seed, the others share its look-ahead votes). offsets has n+1 entries; the instances of seed
  * i are inst[offsets[i] .. offsets[i+1]). Returns LCB_OK, or LCB_ERR (e.g. inst_cap too small: the needed
@@ -362,6 +382,9 @@ int lcb_find_blocks_gpus(const lcb_graph* g, const int* device_ordinals, int n_d
 typedef struct lcb_gpus lcb_gpus;
 lcb_gpus* lcb_gpus_create(const lcb_graph* g, const int* device_ordinals, int n_devices, const lcb_params* p, const lcb_device_opts* opts, int always_comm);
 int lcb_gpus_find_blocks(lcb_gpus* m, const lcb_seed* seeds, int64_t n_seeds, const lcb_hooks* hooks, lcb_block** blocks, int64_t* n_blocks, lcb_stats* stats);
+/* Device i (0 .. n_devices - 1) of the set, for the calls that take one device (lcb_device_enumerate_seeds); owned by the set, not
+ * to be destroyed, and not to be used while an lcb_gpus_find_blocks runs. NULL on error. */
+lcb_device* lcb_gpus_device(lcb_gpus* m, int i);
 void lcb_gpus_destroy(lcb_gpus* m);
 
 /* ---- GenerateOutput (blocksfinder.h:605-670): trimming, blocks_coords.gff (blocksfinder.cpp:141-174) and,

@@ -106,6 +106,12 @@ class JunctionStatsEx(C.Structure):
                 ("peak_device_bytes", C.c_uint64), ("mark_ms", C.c_double), ("passes", C.c_int64)]
 
 
+class SeedStats(C.Structure):
+    """lcb_seed_stats: what lcb_device_enumerate_seeds reports."""
+    _fields_ = [("seeds", C.c_int64), ("vertices", C.c_int64), ("max_count", C.c_int64), ("sort_passes", C.c_int32), ("sort_passes_skipped", C.c_int32),
+                ("device_bytes", C.c_uint64)] + [(n, C.c_double) for n in ("count_ms", "fill_ms", "sort_ms", "copy_ms")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in COUNTER_NAMES]
 
@@ -125,7 +131,7 @@ EXPORTS = [
     "lcb_committer_free", "lcb_committer_commit_phase", "lcb_committer_take_marks", "lcb_committer_n_blocks", "lcb_committer_blocks",
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
-    "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan",
+    "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan", "lcb_device_enumerate_seeds", "lcb_device_sort_seeds", "lcb_gpus_device",
 ]
 
 
@@ -165,6 +171,11 @@ def load_library():
     L.lcb_enumerate_seeds.restype = i64
     L.lcb_enumerate_seeds.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.lcb_free.argtypes = [vp]
+    L.lcb_device_enumerate_seeds.restype = i64
+    L.lcb_device_enumerate_seeds.argtypes = [vp, C.POINTER(vp), C.POINTER(SeedStats)]
+    L.lcb_device_sort_seeds.argtypes = [vp, vp, i64]
+    L.lcb_gpus_device.restype = vp
+    L.lcb_gpus_device.argtypes = [vp, C.c_int]
     L.lcb_device_create.restype = vp
     L.lcb_device_create.argtypes = [vp, C.POINTER(Params), C.c_int]
     L.lcb_device_create_ex.restype = vp
@@ -384,6 +395,24 @@ class Device:
 
     def set_stats_mode(self, on):
         self.L.lcb_device_set_stats_mode(self.h, 1 if on else 0)
+
+    def enumerate_seeds(self, stats=False):
+        """Bundle enumeration + sort on the device's own tables (lcb_device_enumerate_seeds): the array storage.seeds() returns, in
+        the same order. stats=True: (array, dict of lcb_seed_stats)."""
+        out, st = C.c_void_p(), SeedStats()
+        n = self.L.lcb_device_enumerate_seeds(self.h, C.byref(out), C.byref(st))
+        if n < 0:
+            raise _err(self.L)
+        arr = _np_from(out.value, n, SEED_DTYPE)
+        self.L.lcb_free(out)
+        return (arr, {f: getattr(st, f) for f, _ in SeedStats._fields_}) if stats else arr
+
+    def sort_seeds(self, seeds):
+        """A copy of `seeds` in processing order (Bundle::operator<), sorted on the device; seeds with equal keys keep their order."""
+        s = np.array(seeds, dtype=SEED_DTYPE, copy=True)
+        if self.L.lcb_device_sort_seeds(self.h, s.ctypes.data if len(s) else None, len(s)):
+            raise _err(self.L)
+        return s
 
     def process_seeds(self, seeds, counters=False):
         """ProcessVertex::Process (blocksfinder.h:228-310) for a batch -> (offsets[n+1], instances, best_score[n], counters)."""
@@ -609,7 +638,10 @@ class BlocksFinder:
     def FindBlocks(self, minBlockSize, maxBranchSize, maxFlankingSize=None, lookingDepth=8, sampleSize=0, threads=1, device=None,
                    seeds=None, hooks=None, comm=None, **engine):
         """hooks: an api.Hooks (multi-rank all-gather and/or callback engine); device may be None only with callback hooks.
-        engine: tuning knobs of the round engine (ENGINE_KNOBS), e.g. round_phases=7, round_fixed=1, max_views=-1."""
+        engine: tuning knobs of the round engine (ENGINE_KNOBS), e.g. round_phases=7, round_fixed=1, max_views=-1.
+        seeds: None = enumerated on the host with `threads` threads, "device" = enumerated on the device the call runs on, or an array."""
+        if isinstance(seeds, str) and seeds != "device":
+            raise ValueError("seeds=%r: None (host enumeration), \"device\" or an array of seeds" % (seeds,))
         if engine:
             if hooks is None:
                 hooks = Hooks()
@@ -624,7 +656,12 @@ class BlocksFinder:
         own = device is None and not callback_engine
         dev = Device(self.storage, p) if own else device
         try:
-            s = self.storage.seeds(threads) if seeds is None else np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
+            if isinstance(seeds, str):
+                if dev is None:
+                    raise ValueError("seeds=\"device\" needs a device")
+                s = dev.enumerate_seeds()
+            else:
+                s = self.storage.seeds(threads) if seeds is None else np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
             out, n, st = C.c_void_p(), C.c_int64(), Stats()
             if comm is not None:     # native multi-rank path: RCCL all-gather inside the C++ engine
                 rc = self.L.lcb_find_blocks_comm(self.storage.h, dev.h, comm.h, C.byref(p), s.ctypes.data, len(s),

@@ -161,6 +161,23 @@ int64_t lcb_enumerate_seeds(const lcb_graph* g, int threads, lcb_seed** out)
     LCB_CATCH(-1)
 }
 
+int64_t lcb_device_enumerate_seeds(lcb_device* d, lcb_seed** out, lcb_seed_stats* stats)
+{
+    LCB_TRY
+    LCB_NEED(d && out, "lcb_device_enumerate_seeds");
+    return lcb_device_enumerate_seeds_impl(d, out, stats);
+    LCB_CATCH(-1)
+}
+int lcb_device_sort_seeds(lcb_device* d, lcb_seed* seeds, int64_t n)
+{
+    LCB_TRY
+    LCB_NEED(d && (seeds || n == 0), "lcb_device_sort_seeds");
+    if (n < 0) throw LcbError("lcb_device_sort_seeds: n is negative");
+    lcb_device_sort_seeds_impl(d, seeds, n);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
+
 lcb_device* lcb_device_create(const lcb_graph* g, const lcb_params* p, int device_ordinal)
 {
     LCB_TRY
@@ -409,6 +426,13 @@ int lcb_gpus_find_blocks(lcb_gpus* m, const lcb_seed* seeds, int64_t n_seeds, co
     lcb_gpus_find_blocks_impl(m->impl, seeds, n_seeds, tuningOf(hooks), v, stats);
     return giveBlocks(v, blocks, n_blocks);
     LCB_CATCH(LCB_ERR)
+}
+lcb_device* lcb_gpus_device(lcb_gpus* m, int i)
+{
+    LCB_TRY
+    LCB_NEED(m && m->impl, "lcb_gpus_device");
+    return lcb_gpus_device_impl(m->impl, i);
+    LCB_CATCH(nullptr)
 }
 void lcb_gpus_destroy(lcb_gpus* m)
 {

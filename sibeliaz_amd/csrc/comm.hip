@@ -208,6 +208,11 @@ lcb_gpus_impl* lcb_gpus_create_impl(const lcb_graph* g, const int* ordinals, int
 
 void lcb_gpus_destroy_impl(lcb_gpus_impl* m) { delete m; }
 int lcb_gpus_count_impl(const lcb_gpus_impl* m) { return (int)m->dev.size(); }
+lcb_device* lcb_gpus_device_impl(lcb_gpus_impl* m, int i)
+{
+    if (i < 0 || i >= (int)m->dev.size()) throw LcbError("lcb_gpus_device: the set has " + std::to_string(m->dev.size()) + " devices, not one with index " + std::to_string(i));
+    return m->dev[(size_t)i];
+}
 
 void lcb_gpus_find_blocks_impl(lcb_gpus_impl* m, const lcb_seed* seeds, int64_t nSeeds, LcbEngineConfig cfg, std::vector<lcb_block>& blocks, lcb_stats* stats)
 {

@@ -855,6 +855,19 @@ double lcb_device_hbm_triad_impl(lcb_device* h, uint64_t bytes, int reps)
 
 int lcb_device_max_views_impl(lcb_device* h) { return h->impl->maxViews; }
 int lcb_device_ordinal_impl(lcb_device* h) { return h->impl->ordinal; }
+// What seeds.hip reads: the tables the enumeration needs and the stream of the synchronous launches. Not while a call begun with
+// processBegin is in flight (the header's threading rule, checked where it can be).
+LcbSeedView lcb_device_seed_view_impl(lcb_device* h, const char* fn)
+{
+    lcb_device_impl* d = h->impl;
+    if (d->async) throw LcbError(std::string(fn) + ": a process call is in flight on this device");
+    d->use();
+    LcbSeedView v;
+    v.ordinal = d->ordinal; v.stream = (void*)d->stream;
+    v.occStart32 = d->T.occStart32; v.occStart64 = d->T.occStart64; v.occRec = (const void*)d->T.occRec;
+    v.posCh = d->T.posCh; v.posRevCh = d->T.posRevCh; v.segBase = d->T.segBase; v.nVertex = d->T.nVertex;
+    return v;
+}
 int lcb_device_concurrency_impl(lcb_device* h) { return (int)h->impl->ws[0].nSlots; }
 
 void lcb_device_set_stats_impl(lcb_device* h, bool on) { h->impl->stats = on; }

@@ -50,6 +50,21 @@ int64_t lcb_device_big_retries_impl(lcb_device* d);
 void lcb_find_blocks_impl(const lcb_graph* g, lcb_device* d, const lcb_params* p, const lcb_seed* seeds, int64_t nSeeds,
                           const LcbEngineConfig& cfg, std::vector<lcb_block>& blocks, lcb_stats* stats);
 
+// seeds.hip — seed enumeration and ordering on the device's own tables
+struct LcbSeedView {                 // what the enumeration reads of a device (device pointers) and the stream it runs on (a hipStream_t)
+    int ordinal;
+    void* stream;
+    const uint32_t* occStart32;
+    const uint64_t* occStart64;
+    const void* occRec;
+    const uint8_t *posCh, *posRevCh;
+    const uint64_t* segBase;
+    uint32_t nVertex;
+};
+LcbSeedView lcb_device_seed_view_impl(lcb_device* d, const char* fn);     // (device.hip) fn: the caller, for the messages
+int64_t lcb_device_enumerate_seeds_impl(lcb_device* d, lcb_seed** out, lcb_seed_stats* stats);
+void lcb_device_sort_seeds_impl(lcb_device* d, lcb_seed* seeds, int64_t n);
+
 // comm.hip — RCCL all-gather between the ranks of the round engine
 struct lcb_comm;
 void lcb_comm_unique_id_impl(unsigned char* id128);
@@ -66,5 +81,6 @@ lcb_gpus_impl* lcb_gpus_create_impl(const lcb_graph* g, const int* ordinals, int
 void lcb_gpus_find_blocks_impl(lcb_gpus_impl* m, const lcb_seed* seeds, int64_t nSeeds, LcbEngineConfig cfg, std::vector<lcb_block>& blocks, lcb_stats* stats);
 void lcb_gpus_destroy_impl(lcb_gpus_impl* m);
 int lcb_gpus_count_impl(const lcb_gpus_impl* m);
+lcb_device* lcb_gpus_device_impl(lcb_gpus_impl* m, int i);
 
 #endif

@@ -4,7 +4,8 @@
 // `sibeliaz` wrapper script keeps working verbatim:
 //   sibeliaz-lcb --graph <junctions> <fasta...> -k <odd> -b <int> -o <dir> -m <int> -t <int> --abundance <int> [--noseq] --chunks <int>
 // `-t` stays "host threads" (loading, seed enumeration); the GPU is chosen by the environment
-// (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag.
+// (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag, and so is the place where the seeds are
+// enumerated (LCB_SEEDS=host, the default, or device).
 // The block finder itself runs on the MI355X through the C ABI in include/lcb.h.
 #include <cstdio>
 #include <cstdlib>
@@ -106,8 +107,17 @@ Args parse(int argc, char** argv)
 int main(int argc, char** argv)
 {
     const Args a = parse(argc, argv);
+    // where the seeds are enumerated: chosen like the GPU, from the environment; refused before anything is loaded
+    const char* seedsEnv = getenv("LCB_SEEDS");
+    const std::string seedRoute = seedsEnv && *seedsEnv ? seedsEnv : "host";
+    if (seedRoute != "host" && seedRoute != "device") {
+        std::cerr << "error: LCB_SEEDS is '" << seedRoute << "': it is host (the default) or device" << std::endl;
+        return 1;
+    }
+    const bool deviceSeeds = seedRoute == "device";
     lcb_graph* g = nullptr;
     lcb_device* dev = nullptr;
+    lcb_gpus* set = nullptr;
     lcb_seed* seeds = nullptr;
     lcb_block* blocks = nullptr;
     int rc = 0;
@@ -122,30 +132,50 @@ int main(int argc, char** argv)
         lcb_params p;
         p.k = (int)a.k; p.min_block = (int)a.m; p.max_branch = (int)a.b; p.max_flank = (int)a.b;   // sibeliaz.cpp:133-138
         p.looking_depth = 8; p.phase_size = 256;
-        const int64_t nSeeds = lcb_enumerate_seeds(g, (int)a.t, &seeds);
-        if (nSeeds < 0) { fail(); break; }
         // GPU selection comes from the environment, never from argv (the wrapper's command line, sibeliaz:146, stays as it is):
         // LCB_GPUS=N uses HIP devices 0..N-1 (as filtered by HIP_VISIBLE_DEVICES), LCB_DEVICE=i uses device i; default one GPU.
+        // So does the seed route: LCB_SEEDS=host (default) enumerates with -t host threads before the device exists, LCB_SEEDS=device
+        // creates the device first and enumerates on its tables (with LCB_GPUS=N on device 0 of the set).
         const char* devEnv = getenv("LCB_DEVICE");
         const char* gpusEnv = getenv("LCB_GPUS");
         const int nGpus = gpusEnv && *gpusEnv ? atoi(gpusEnv) : 1;
+        auto createDevices = [&]() -> bool {
+            if (nGpus > 1) {
+                std::vector<int> ord;
+                for (int i = 0; i < nGpus; i++) ord.push_back(i);
+                // the same handle bench.py --gpus N times: devices + tables + RCCL once, then one pass
+                set = lcb_gpus_create(g, ord.data(), nGpus, &p, nullptr, 0);
+                return set != nullptr;
+            }
+            dev = lcb_device_create(g, &p, devEnv && *devEnv ? atoi(devEnv) : 0);
+            return dev != nullptr;
+        };
+        int64_t nSeeds = -1;
+        if (deviceSeeds) {
+            if (!createDevices()) { fail(); break; }
+            lcb_device* d0 = nGpus > 1 ? lcb_gpus_device(set, 0) : dev;
+            if (!d0) { fail(); break; }
+            lcb_seed_stats ss;
+            nSeeds = lcb_device_enumerate_seeds(d0, &seeds, &ss);
+            if (nSeeds >= 0 && getenv("LCB_VERBOSE"))
+                std::cerr << "lcb: device seeds=" << ss.seeds << " vertices=" << ss.vertices << " max_count=" << ss.max_count << " sort_passes=" << ss.sort_passes << " (+"
+                          << ss.sort_passes_skipped << " skipped) device_bytes=" << ss.device_bytes << " count_ms=" << ss.count_ms << " fill_ms=" << ss.fill_ms
+                          << " sort_ms=" << ss.sort_ms << " copy_ms=" << ss.copy_ms << std::endl;
+        } else
+            nSeeds = lcb_enumerate_seeds(g, (int)a.t, &seeds);
+        if (nSeeds < 0) { fail(); break; }
+        if (!deviceSeeds && !createDevices()) { fail(); break; }
         int64_t nBlocks = 0;
         lcb_stats st;
         if (nGpus > 1) {
-            std::vector<int> ord;
-            for (int i = 0; i < nGpus; i++) ord.push_back(i);
             lcb_hooks hk;
             memset(&hk, 0, sizeof(hk));
             hk.abi = LCB_ABI_VERSION; hk.world = 1; hk.progress = 1;
-            // the same handle bench.py --gpus N times: devices + tables + RCCL once, then one pass
-            lcb_gpus* set = lcb_gpus_create(g, ord.data(), nGpus, &p, nullptr, 0);
-            if (!set) { fail(); break; }
             const int rc = lcb_gpus_find_blocks(set, seeds, nSeeds, &hk, &blocks, &nBlocks, &st);
             lcb_gpus_destroy(set);
+            set = nullptr;
             if (rc != LCB_OK) { fail(); break; }
         } else {
-            dev = lcb_device_create(g, &p, devEnv && *devEnv ? atoi(devEnv) : 0);
-            if (!dev) { fail(); break; }
             if (lcb_find_blocks(g, dev, &p, seeds, nSeeds, 1, &blocks, &nBlocks, &st) != LCB_OK) { fail(); break; }
         }
         if (getenv("LCB_VERBOSE"))
@@ -166,6 +196,7 @@ int main(int argc, char** argv)
     } while (false);
     lcb_free(blocks);
     lcb_free(seeds);
+    lcb_gpus_destroy(set);
     lcb_device_destroy(dev);
     lcb_graph_free(g);
     return rc;
