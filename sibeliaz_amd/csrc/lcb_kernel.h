@@ -47,7 +47,7 @@
 #include "lcb_kernel_limits.h"
 
 #define LCB_EMPTY_KEY INT32_MIN
-// s_waitcnt vmcnt(0) (gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15), see lcb_vote_walk
+// s_waitcnt vmcnt(0) (gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15), see lcb_vote_walk_windows
 #if defined(__HIP_DEVICE_COMPILE__)
 #define LCB_NO_LOADS_IN_FLIGHT() __builtin_amdgcn_s_waitcnt(0x0F70)
 #else
@@ -79,18 +79,21 @@
 //   mode 2 "big":     4096 / 4096: ordered index, lists and vote table in LDS, the instance fields in the global workspace
 //   mode 3 "huge":    everything in the global workspace, capacities chosen (and grown) by the host
 // IC instances, VC vote slots, BW Bloom words (0 = none), PC path-set slots in LDS (0 = global workspace)
+// Who votes how (the vote section below; both decided by same-box A/B on the MI355X, profiles/r06 and profiles/heavy_vote):
+// WINDOW_WALK  the voters are walked by the window-table walk (lcb_vote_walk_windows), else by the ticket walk (lcb_vote_walk_tickets)
+// RESOLVE      heavy votes in workgroups of more than two wavefronts are resolved by wave 0 and dealt as items (lcb_vote_resolve)
 template <int MODE> struct LcbCfg;
 // Idx: a pool index / a vote-table slot (16 bits where the capacities are compile-time constants of a few thousand; 32 bits in the huge
 // variant, whose capacities grow with the path - the reference's vectors are unbounded, path.h:683-685); VLast: (ordinal of the last
 // contributing instance in the voting list, step) of a vote-table entry - 16 + 16 bits, or 32 + 32.
-template <> struct LcbCfg<0> { static constexpr uint32_t IC = 256, VC = 1024, BW = 256, PC = 0; static constexpr bool INST_LDS = true, IDX_LDS = true; typedef uint16_t Idx; typedef uint32_t VLast; };
-template <> struct LcbCfg<1> { static constexpr uint32_t IC = 1024, VC = 2048, BW = 0, PC = 8192; static constexpr bool INST_LDS = true, IDX_LDS = true; typedef uint16_t Idx; typedef uint32_t VLast; };
-template <> struct LcbCfg<2> { static constexpr uint32_t IC = 4096, VC = 4096, BW = 2048, PC = 0; static constexpr bool INST_LDS = false, IDX_LDS = true; typedef uint16_t Idx; typedef uint32_t VLast; };
+template <> struct LcbCfg<0> { static constexpr uint32_t IC = 256, VC = 1024, BW = 256, PC = 0; static constexpr bool INST_LDS = true, IDX_LDS = true, WINDOW_WALK = true, RESOLVE = false; typedef uint16_t Idx; typedef uint32_t VLast; };
+template <> struct LcbCfg<1> { static constexpr uint32_t IC = 1024, VC = 2048, BW = 0, PC = 8192; static constexpr bool INST_LDS = true, IDX_LDS = true, WINDOW_WALK = false, RESOLVE = true; typedef uint16_t Idx; typedef uint32_t VLast; };
+template <> struct LcbCfg<2> { static constexpr uint32_t IC = 4096, VC = 4096, BW = 2048, PC = 0; static constexpr bool INST_LDS = false, IDX_LDS = true, WINDOW_WALK = false, RESOLVE = true; typedef uint16_t Idx; typedef uint32_t VLast; };
 // 4 = the compact variant with half the pools (128 instances / 512 vote slots: 17 KB of LDS instead of 32 KB - 8 workgroups per CU, bound by
 // registers, instead of 5): where the vertices have few occurrences (k = 25 inputs of 8-16 genomes: paths of ~16 instances) the round launches
 // of a Gbp-scale input are bound by the number of seeds in flight (profiles/r06). For the host it is variant 0 (lcb_device_opts.compact_pools).
-template <> struct LcbCfg<4> { static constexpr uint32_t IC = 128, VC = 512, BW = 256, PC = 0; static constexpr bool INST_LDS = true, IDX_LDS = true; typedef uint16_t Idx; typedef uint32_t VLast; };
-template <> struct LcbCfg<3> { static constexpr uint32_t IC = 1, VC = 1, BW = 2048, PC = 0; static constexpr bool INST_LDS = false, IDX_LDS = false; typedef uint32_t Idx; typedef unsigned long long VLast; };
+template <> struct LcbCfg<4> { static constexpr uint32_t IC = 128, VC = 512, BW = 256, PC = 0; static constexpr bool INST_LDS = true, IDX_LDS = true, WINDOW_WALK = true, RESOLVE = false; typedef uint16_t Idx; typedef uint32_t VLast; };
+template <> struct LcbCfg<3> { static constexpr uint32_t IC = 1, VC = 1, BW = 2048, PC = 0; static constexpr bool INST_LDS = false, IDX_LDS = false, WINDOW_WALK = false, RESOLVE = false; typedef uint32_t Idx; typedef unsigned long long VLast; };
 
 enum LcbStatus : uint32_t {
     LCB_ST_OK = 0,
@@ -669,6 +672,14 @@ __device__ inline void lcb_path_init(ST& S, int32_t vid, int32_t ch)
 
 // ---- the vote: MostPopularVertex (blocksfinder.h:708-768) --------------------------------------
 // One voter = one instance whose end vertex is the path end (blocksfinder.h:716-717). Its scalars live in SGPRs.
+// Which function is which stage (which variant takes which: the LcbCfg table):
+//   lcb_vote, lcb_vote_pass     the attempts of one MostPopularVertex; one pass of it: barrier A, walk, B, arg-max and clearing (shared: C, D)
+//   lcb_vote_walk               a wavefront's voters into the vote table: lcb_vote_walk_tickets (wide, big, huge: voter by voter, chunk by
+//                               chunk) or lcb_vote_walk_windows (compact: stage A, the windows of 64 voters at once; stage B, their items)
+//   lcb_used_fetch8 / _first    the pure parts of stage A: the bitmap words of a window, the first used step in them
+//   lcb_voter_request / _resolve, lcb_vote_resolve / _items   stage A per voter, for the heavy vote of wide and big: wave 0 resolves the
+//                               whole touch list before barrier A, all wavefronts draw the items after it
+//   lcb_vote_add                the one insert into the vote table that all of them end in
 
 // The voter walks of one vote. The voters are the instances of the touch list that are in the voting list (the good list
 // if it has two entries, else all instances; blocksfinder.h:713). With two wavefronts wave w takes the voters with ordinal == w
@@ -687,16 +698,50 @@ __device__ inline void lcb_path_init(ST& S, int32_t vid, int32_t ch)
 // with the path set in LDS always walk exactly.
 // (Tried and measured slower on the MI355X, profiles/r03: requesting the next chunk of a voter ahead of time with unconditional,
 // straight-line loads - the main wavefront is bound by instruction issue, not by the round trips the prefetch hides.)
-// ---- The round-5 walk - one voter after the other, chunk by chunk, voters drawn from LDS tickets. Which kernel variant walks which way is a
-// bit mask over the variants (bit m set: variant m takes the window-table walk below); decided by same-box A/B on the MI355X (profiles/r06).
-#ifndef LCB_WALK_V2_MODES
-#define LCB_WALK_V2_MODES 0x11u
-#endif
-#define LCB_WALK_V2_OF(ST) (((LCB_WALK_V2_MODES) >> ST::MODE) & 1u)
+// ---- The ticket walk (round 5) - one voter after the other, chunk by chunk, voters drawn from LDS tickets.
 template <class F> struct LcbVoterT { uint32_t e, i, g0, pos0, lo, rem, weight; int32_t dir; bool positive; F sb; };   // sb: base of the voter's segment
 struct LcbWalk { uint32_t g, pos; int32_t id; uint32_t uw; bool valid; };
+
+// A voter from the (wave-uniform) fields of its instance: e its position in the voting list, i its pool index, (g0, pos0) the end it
+// walks from, [lo, hi) its chromosome, fl its flag word.
+template <class ST>
+__device__ __forceinline__ LcbVoterT<typename ST::Flat> lcb_voter_of(const ST& S, bool forward, uint32_t e, uint32_t i, uint32_t g0, uint32_t pos0, uint32_t lo, uint32_t hi,
+                                                                     uint32_t weight, uint32_t fl)
+{
+    typedef typename ST::Flat Flat;
+    LcbVoterT<Flat> v;
+    v.e = e; v.i = i; v.g0 = g0; v.pos0 = pos0; v.lo = lo; v.weight = weight;
+    v.positive = (fl & LCB_FLAG_POS) != 0;
+    v.dir = (forward == v.positive) ? 1 : -1;
+    v.rem = v.dir > 0 ? hi - 1u - g0 : g0 - lo;                    // steps for which it.Valid() holds
+    v.sb = ST::SEG ? (Flat)lcb_rfl(S.segBase[lcb_fl_seg(fl)]) : (Flat)0;
+    return v;
+}
+
+// The vote-table insert of every walk, per lane: vertex `vid` gets `weight` from the voter at position e of the voting list, d steps from
+// its origin. Probe, claim of an empty slot into the touched list (a full list or table sets the overflow flag), weight, last contribution
+// in list order. (vmask = voteCap - 1, claimCap = 3/4 voteCap: wave-uniform, computed once per walk by the caller.)
+template <class ST>
+__device__ __forceinline__ void lcb_vote_add(ST& S, uint32_t vmask, uint32_t claimCap, int32_t vid, uint32_t weight, uint32_t e, uint32_t d)
+{
+    uint32_t h = lcb_hash(vid, S.voteShift);
+    int32_t old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
+    uint32_t probe = 0;
+    while (old != LCB_EMPTY_KEY && old != vid && probe < S.voteCap) {
+        h = (h + 1) & vmask; probe++;
+        old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
+    }
+    if (old == LCB_EMPTY_KEY) {
+        const uint32_t t = atomicAdd(S.vNClaimed, 1u);
+        if (t < claimCap) S.vTouched[t] = (typename ST::Idx)h; else *S.vOvf = 1u;
+    }
+    if (old == LCB_EMPTY_KEY || old == vid) {
+        atomicAdd(&S.vCount[h], weight);
+        atomicMax(&S.vLast[h], ((typename ST::VLast)e << ST::LAST_SHIFT) | d);
+    } else *S.vOvf = 1u;
+}
 template <bool STATS, bool PROF = false, class ST>
-__device__ inline void lcb_vote_walk_v1(ST& S, bool forward, bool tryUsed, bool useGood, uint32_t waveId, uint32_t nWaves, bool exact)
+__device__ inline void lcb_vote_walk_tickets(ST& S, bool forward, bool tryUsed, bool useGood, uint32_t waveId, uint32_t nWaves, bool exact)
 {
     const LcbTables& T = S.T;
     typedef typename ST::Flat Flat;
@@ -724,17 +769,9 @@ __device__ inline void lcb_vote_walk_v1(ST& S, bool forward, bool tryUsed, bool 
                 const uint32_t e = useGood ? lcb_rfl((uint32_t)S.goodPos[i]) : i;      // position in the voting list (its order breaks ties)
                 if (e == ST::NONE) continue;
                 const uint32_t f = lcb_inst_fields(S, i);
-                const uint32_t fl = lcb_rl(f, LCB_F_FLAGS), fp = lcb_rl(f, LCB_F_FRONTPOS), bp = lcb_rl(f, LCB_F_BACKPOS);
-                v.e = e; v.i = i;
-                v.g0 = forward ? lcb_rl(f, LCB_F_BACKG) : lcb_rl(f, LCB_F_FRONTG);
-                v.pos0 = forward ? bp : fp;
-                v.lo = lcb_rl(f, LCB_F_LO);
-                const uint32_t hi = lcb_rl(f, LCB_F_HI);
-                v.weight = lcb_absdiff(fp, bp) + 1u;                                   // blocksfinder.h:719
-                v.positive = (fl & LCB_FLAG_POS) != 0;
-                v.dir = (forward == v.positive) ? 1 : -1;
-                v.rem = v.dir > 0 ? hi - 1u - v.g0 : v.g0 - v.lo;                      // steps for which it.Valid() holds
-                v.sb = ST::SEG ? (Flat)lcb_rfl(S.segBase[lcb_fl_seg(fl)]) : (Flat)0;
+                const uint32_t fp = lcb_rl(f, LCB_F_FRONTPOS), bp = lcb_rl(f, LCB_F_BACKPOS);
+                v = lcb_voter_of(S, forward, e, i, forward ? lcb_rl(f, LCB_F_BACKG) : lcb_rl(f, LCB_F_FRONTG), forward ? bp : fp, lcb_rl(f, LCB_F_LO), lcb_rl(f, LCB_F_HI),
+                                 lcb_absdiff(fp, bp) + 1u, lcb_rl(f, LCB_F_FLAGS));    // (weight: blocksfinder.h:719)
                 return true;
             }
         }
@@ -764,15 +801,7 @@ __device__ inline void lcb_vote_walk_v1(ST& S, bool forward, bool tryUsed, bool 
             pend &= pend - 1;
             const uint32_t o = ordinal++;
             if (nWaves > 1 && (o % nWaves) != waveId) continue;
-            v.e = lcb_rl(fE, b);
-            v.i = lcb_rl(fI, b); v.g0 = lcb_rl(fG, b); v.pos0 = lcb_rl(fPos, b); v.lo = lcb_rl(fLo, b);
-            const uint32_t hi = lcb_rl(fHi, b);
-            v.weight = lcb_rl(fW, b);
-            const uint32_t vfl = lcb_rl(fFl, b);
-            v.positive = (vfl & LCB_FLAG_POS) != 0;
-            v.dir = (forward == v.positive) ? 1 : -1;
-            v.rem = v.dir > 0 ? hi - 1u - v.g0 : v.g0 - v.lo;                               // steps for which it.Valid() holds
-            v.sb = ST::SEG ? (Flat)lcb_rfl(S.segBase[lcb_fl_seg(vfl)]) : (Flat)0;
+            v = lcb_voter_of(S, forward, lcb_rl(fE, b), lcb_rl(fI, b), lcb_rl(fG, b), lcb_rl(fPos, b), lcb_rl(fLo, b), lcb_rl(fHi, b), lcb_rl(fW, b), lcb_rl(fFl, b));
             return true;
         }
     };
@@ -817,23 +846,7 @@ __device__ inline void lcb_vote_walk_v1(ST& S, bool forward, bool tryUsed, bool 
                 const bool breaking = stopM && (uint32_t)(__ffsll((long long)stopM) - 1) == first;
                 if (S.lane < first || (S.lane == first && breaking)) S.cWalk++;
             }
-            if (S.lane < first) {
-                uint32_t h = lcb_hash(vid, S.voteShift);
-                int32_t old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
-                uint32_t probe = 0;
-                while (old != LCB_EMPTY_KEY && old != vid && probe < S.voteCap) {
-                    h = (h + 1) & vmask; probe++;
-                    old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
-                }
-                if (old == LCB_EMPTY_KEY) {
-                    const uint32_t t = atomicAdd(S.vNClaimed, 1u);
-                    if (t < claimCap) S.vTouched[t] = (typename ST::Idx)h; else *S.vOvf = 1u;
-                }
-                if (old == LCB_EMPTY_KEY || old == vid) {
-                    atomicAdd(&S.vCount[h], cur.weight);
-                    atomicMax(&S.vLast[h], ((typename ST::VLast)cur.e << ST::LAST_SHIFT) | d);
-                } else *S.vOvf = 1u;
-            }
+            if (S.lane < first) lcb_vote_add(S, vmask, claimCap, vid, cur.weight, cur.e, d);
             if (first < 64) {
                 if (!tryUsed && S.lane == 0) {
                     // steps 1 .. c*64+first-1 read used == 0 (one step of slack keeps the - strand's bit g-1 inside)
@@ -882,10 +895,65 @@ __host__ __device__ inline uint32_t lcb_brev32(uint32_t x)
 }
 #define LCB_BREV32(x) lcb_brev32(x)
 
-template <bool STATS, bool PROF = false, class ST>
-__device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool useGood, uint32_t waveId, uint32_t nWaves, bool exact)
+// Stage A's two pure parts. IsUsed of step d of a walk: + strand bit g, - strand bit g - 1 (none at the chromosome start). The bits of
+// steps 1, 2, ... in walking order are flat bit fb, then fb + 1, ... (up) or fb - 1, ... (down); 8 words of it cover at least 225 steps.
+// Word fetch: those eight words through the view's page table. Indices stop at maxW (the bitmap has nPos / 32 + 2 words) and at 0.
+template <class F>
+__device__ __forceinline__ void lcb_used_fetch8(const LcbUsed& U, F fb, bool up, uint32_t maxW, uint32_t (&uw)[8])
 {
-    if (!LCB_WALK_V2_OF(ST)) { lcb_vote_walk_v1<STATS, PROF>(S, forward, tryUsed, useGood, waveId, nWaves, exact); return; }
+    const uint32_t W0 = (uint32_t)(fb >> 5);
+    const uint32_t um = up ? 0xFFFFFFFFu : 0u;       // (selects by mask, not by branch: the eight addresses are straight-line code)
+    uint32_t a[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) a[k] = (((W0 + k) < maxW ? (W0 + k) : maxW) & um) | ((W0 - (W0 < k ? W0 : k)) & ~um);
+    if (U.tab) {
+        const auto tab = LCB_GLOBAL_U32(U.tab);
+        uint32_t o[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) o[k] = tab[a[k] >> LCB_PAGE_SHIFT];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) a[k] += o[k];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) uw[k] = U.live[a[k]];
+}
+
+// Scan: the first used step (1-based, 0 = none) among steps 1 .. L of a walk of `rem` valid steps; steps past the eight words uw
+// (windows of more than 225 steps: -b beyond 225) are read bit by bit from U.
+template <class F>
+__device__ __forceinline__ uint32_t lcb_used_first(const LcbUsed& U, const uint32_t (&uw)[8], F fb, bool up, bool positive, uint32_t L, uint32_t rem)
+{
+    const uint32_t Lu = (!positive && !up && L == rem) ? L - 1u : L;   // the step onto the chromosome's first position reads no bit on the - strand
+    const uint32_t sh = up ? ((uint32_t)fb & 31u) : 31u - ((uint32_t)fb & 31u);
+    uint32_t w[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) w[k] = uw[k];
+    if (!up) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) w[k] = LCB_BREV32(w[k]);
+    }
+    const uint64_t s0 = (uint64_t)w[0] | ((uint64_t)w[1] << 32), s1 = (uint64_t)w[2] | ((uint64_t)w[3] << 32), s2 = (uint64_t)w[4] | ((uint64_t)w[5] << 32), s3 = (uint64_t)w[6] | ((uint64_t)w[7] << 32);
+    const uint64_t x[4] = { (s0 >> sh) | ((s1 << 1) << (63u - sh)), (s1 >> sh) | ((s2 << 1) << (63u - sh)), (s2 >> sh) | ((s3 << 1) << (63u - sh)), s3 >> sh };
+    const uint32_t have = 256u - sh;                   // steps whose bit is in x[0] .. x[3]
+    const uint32_t n = Lu < have ? Lu : have;
+    uint32_t first = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t base = 64u * k;
+        if (!first && n > base) {
+            const uint32_t c = n - base < 64u ? n - base : 64u;
+            const uint64_t m = x[k] & (c == 64u ? ~0ull : ((1ull << c) - 1ull));
+            if (m) first = base + (uint32_t)__ffsll((long long)m);
+        }
+    }
+    for (uint32_t d = have + 1; !first && d <= Lu; d++)
+        if (lcb_used_bit(U, (F)(up ? fb + (d - 1u) : fb - (d - 1u)))) first = d;
+    return first;
+}
+
+template <bool STATS, bool PROF = false, class ST>
+__device__ inline void lcb_vote_walk_windows(ST& S, bool forward, bool tryUsed, bool useGood, uint32_t waveId, uint32_t nWaves, bool exact)
+{
     const LcbTables& T = S.T;
     typedef typename ST::Flat Flat;
     const uint32_t vmask = S.voteCap - 1;
@@ -922,27 +990,11 @@ __device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool use
         const bool walks = isV && rem != 0;
         uint32_t win = 0;
         if (walks) win = T.posWin[f0];
-        // IsUsed of step d: + strand bit g, - strand bit g - 1 (none at the chromosome start). The bits of steps 1, 2, ... in walking
-        // order: flat bit fb, then fb + 1, ... (up) or fb - 1, ... (down); 8 words of it cover at least 225 steps.
-        const uint32_t delta = positive ? 0u : 1u;
+        const uint32_t delta = positive ? 0u : 1u;                 // (the bit of step 1: lcb_used_fetch8)
         const bool scan = walks && !tryUsed && !(!up && f0 < (Flat)(1u + delta));   // (down from flat position 0 / 1 on the - strand: no step has a bit)
         const Flat fb = scan ? (up ? f0 + 1u - delta : f0 - 1u - delta) : (Flat)0;
-        uint32_t uw0 = 0, uw1 = 0, uw2 = 0, uw3 = 0, uw4 = 0, uw5 = 0, uw6 = 0, uw7 = 0;
-        if (scan) {
-            const uint32_t W0 = (uint32_t)(fb >> 5);
-            const uint32_t um = up ? 0xFFFFFFFFu : 0u;       // (selects by mask, not by branch: the eight addresses are straight-line code)
-#define LCB_WIDX(k) ((((W0 + (k)) < maxW ? (W0 + (k)) : maxW) & um) | ((W0 - (W0 < (k) ? W0 : (k))) & ~um))
-            uint32_t a0 = LCB_WIDX(0u), a1 = LCB_WIDX(1u), a2 = LCB_WIDX(2u), a3 = LCB_WIDX(3u), a4 = LCB_WIDX(4u), a5 = LCB_WIDX(5u), a6 = LCB_WIDX(6u), a7 = LCB_WIDX(7u);
-#undef LCB_WIDX
-            if (S.U.tab) {
-                const auto tab = LCB_GLOBAL_U32(S.U.tab);
-                const uint32_t o0 = tab[a0 >> LCB_PAGE_SHIFT], o1 = tab[a1 >> LCB_PAGE_SHIFT], o2 = tab[a2 >> LCB_PAGE_SHIFT], o3 = tab[a3 >> LCB_PAGE_SHIFT];
-                const uint32_t o4 = tab[a4 >> LCB_PAGE_SHIFT], o5 = tab[a5 >> LCB_PAGE_SHIFT], o6 = tab[a6 >> LCB_PAGE_SHIFT], o7 = tab[a7 >> LCB_PAGE_SHIFT];
-                a0 += o0; a1 += o1; a2 += o2; a3 += o3; a4 += o4; a5 += o5; a6 += o6; a7 += o7;
-            }
-            uw0 = S.U.live[a0]; uw1 = S.U.live[a1]; uw2 = S.U.live[a2]; uw3 = S.U.live[a3];
-            uw4 = S.U.live[a4]; uw5 = S.U.live[a5]; uw6 = S.U.live[a6]; uw7 = S.U.live[a7];
-        }
+        uint32_t uw[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        if (scan) lcb_used_fetch8(S.U, fb, up, maxW, uw);
         // ---- the first chunks of the first LCB_VB voters are requested now, before their windows are known
         unsigned long long pend = __ballot(walks);
         const unsigned long long walkM = pend;
@@ -972,19 +1024,7 @@ __device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool use
             if (L > rem) L = rem;
             nv = L;
             if (scan) {
-                const uint32_t Lu = (!positive && !up && L == rem) ? L - 1u : L;   // the step onto the chromosome's first position reads no bit on the - strand
-                const uint32_t sh = up ? ((uint32_t)fb & 31u) : 31u - ((uint32_t)fb & 31u);
-                if (!up) { uw0 = LCB_BREV32(uw0); uw1 = LCB_BREV32(uw1); uw2 = LCB_BREV32(uw2); uw3 = LCB_BREV32(uw3); uw4 = LCB_BREV32(uw4); uw5 = LCB_BREV32(uw5); uw6 = LCB_BREV32(uw6); uw7 = LCB_BREV32(uw7); }
-                const uint64_t s0 = (uint64_t)uw0 | ((uint64_t)uw1 << 32), s1 = (uint64_t)uw2 | ((uint64_t)uw3 << 32), s2 = (uint64_t)uw4 | ((uint64_t)uw5 << 32), s3 = (uint64_t)uw6 | ((uint64_t)uw7 << 32);
-                const uint64_t x0 = (s0 >> sh) | ((s1 << 1) << (63u - sh)), x1 = (s1 >> sh) | ((s2 << 1) << (63u - sh)), x2 = (s2 >> sh) | ((s3 << 1) << (63u - sh)), x3 = s3 >> sh;
-                const uint32_t have = 256u - sh;                   // steps whose bit is in x0 .. x3
-                const uint32_t n = Lu < have ? Lu : have;
-                uint32_t first = 0;                                // first used step (1-based), 0 = none
-#define LCB_SCAN64(x, base) if (!first && n > (base)) { const uint32_t c_ = n - (base) < 64u ? n - (base) : 64u; const uint64_t m_ = (x) & (c_ == 64u ? ~0ull : ((1ull << c_) - 1ull)); if (m_) first = (base) + (uint32_t)__ffsll((long long)m_); }
-                LCB_SCAN64(x0, 0u) LCB_SCAN64(x1, 64u) LCB_SCAN64(x2, 128u) LCB_SCAN64(x3, 192u)
-#undef LCB_SCAN64
-                for (uint32_t d = have + 1; !first && d <= Lu; d++)    // (windows of more than 225 steps: -b beyond 225)
-                    if (lcb_used_bit(S.U, (Flat)(up ? fb + (d - 1u) : fb - (d - 1u)))) first = d;
+                const uint32_t first = lcb_used_first(S.U, uw, fb, up, positive, L, rem);
                 if (first) { nv = first - 1u; brk = 1u; }
             }
         }
@@ -1018,23 +1058,7 @@ __device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool use
                 }
             }
             const uint32_t wgt = lcb_rl(weight, b), e = lcb_rl(vE, b);
-            if (act) {
-                uint32_t h = lcb_hash(vid, S.voteShift);
-                int32_t old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
-                uint32_t probe = 0;
-                while (old != LCB_EMPTY_KEY && old != vid && probe < S.voteCap) {
-                    h = (h + 1) & vmask; probe++;
-                    old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
-                }
-                if (old == LCB_EMPTY_KEY) {
-                    const uint32_t tt = atomicAdd(S.vNClaimed, 1u);
-                    if (tt < claimCap) S.vTouched[tt] = (typename ST::Idx)h; else *S.vOvf = 1u;
-                }
-                if (old == LCB_EMPTY_KEY || old == vid) {
-                    atomicAdd(&S.vCount[h], wgt);
-                    atomicMax(&S.vLast[h], ((typename ST::VLast)e << ST::LAST_SHIFT) | d);
-                } else *S.vOvf = 1u;
-            }
+            if (act) lcb_vote_add(S, vmask, claimCap, vid, wgt, e, d);
         };
         // the items behind the speculative ones, in voter order: chunk 1 ... of the first LCB_VB voters, every chunk of the others
         unsigned long long rest = walkM;
@@ -1067,16 +1091,26 @@ __device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool use
     }
 }
 
-// Stage A of lcb_vote_walk as two functions, for the resolved heavy vote of the wide and big variants below (lcb_vote_resolve). The
-// compact walk keeps its own inlined copy: calling these from it moved the register allocation of the compact kernels (SGPR spills
-// 292 -> 266 / 402 -> 421, a compact vote +1 % in the instrumented pass), and the k = 25 shapes run almost entirely there.
+// The voter walks of one wavefront, as the variant table says.
+template <bool STATS, bool PROF = false, class ST>
+__device__ inline void lcb_vote_walk(ST& S, bool forward, bool tryUsed, bool useGood, uint32_t waveId, uint32_t nWaves, bool exact)
+{
+    if (LcbCfg<ST::MODE>::WINDOW_WALK) lcb_vote_walk_windows<STATS, PROF>(S, forward, tryUsed, useGood, waveId, nWaves, exact);
+    else lcb_vote_walk_tickets<STATS, PROF>(S, forward, tryUsed, useGood, waveId, nWaves, exact);
+}
+
+// Stage A of the window-table walk as two functions, for the resolved heavy vote of the wide and big variants below (lcb_vote_resolve).
+// Shared with the compact walk: the word fetch and the scan (lcb_used_fetch8, lcb_used_first). Deliberately not shared: the ORDER of the
+// requests. The compact walk asks for fields, window word, bitmap words and then the ids of its first LCB_VB voters before it scans -
+// that order is the point of that walk - and its text is what the compact kernels' register allocation hangs on
+// (profiles/heavy_vote section 1, profiles/vote_refactor).
 // First half, the requests. Entry t of the touch list: its instance fields, its window word and the eight bitmap words its window
 // can cover, all requested together (nothing is consumed here).
 template <class F> struct LcbVoterReq {
     bool isV, walks, scan, positive, up;
     uint32_t vI, vE, g0, rem, weight, fl, win;
     F fb;                                                          // flat bit of step 1 (scan)
-    uint32_t uw0, uw1, uw2, uw3, uw4, uw5, uw6, uw7;
+    uint32_t uw[8];
 };
 template <class ST>
 __device__ __forceinline__ LcbVoterReq<typename ST::Flat> lcb_voter_request(const ST& S, uint32_t t, uint32_t nTouch, bool forward, bool tryUsed, bool useGood, uint32_t maxW)
@@ -1106,27 +1140,11 @@ __device__ __forceinline__ LcbVoterReq<typename ST::Flat> lcb_voter_request(cons
     R.walks = R.isV && R.rem != 0;
     R.win = 0;
     if (R.walks) R.win = T.posWin[f0];
-    // IsUsed of step d: + strand bit g, - strand bit g - 1 (none at the chromosome start). The bits of steps 1, 2, ... in walking
-    // order: flat bit fb, then fb + 1, ... (up) or fb - 1, ... (down); 8 words of it cover at least 225 steps.
-    const uint32_t delta = R.positive ? 0u : 1u;
+    const uint32_t delta = R.positive ? 0u : 1u;                   // (the bit of step 1: lcb_used_fetch8)
     R.scan = R.walks && !tryUsed && !(!R.up && f0 < (Flat)(1u + delta));   // (down from flat position 0 / 1 on the - strand: no step has a bit)
     R.fb = R.scan ? (R.up ? f0 + 1u - delta : f0 - 1u - delta) : (Flat)0;
-    R.uw0 = 0; R.uw1 = 0; R.uw2 = 0; R.uw3 = 0; R.uw4 = 0; R.uw5 = 0; R.uw6 = 0; R.uw7 = 0;
-    if (R.scan) {
-        const uint32_t W0 = (uint32_t)(R.fb >> 5);
-        const uint32_t um = R.up ? 0xFFFFFFFFu : 0u;       // (selects by mask, not by branch: the eight addresses are straight-line code)
-#define LCB_WIDX(k) ((((W0 + (k)) < maxW ? (W0 + (k)) : maxW) & um) | ((W0 - (W0 < (k) ? W0 : (k))) & ~um))
-        uint32_t a0 = LCB_WIDX(0u), a1 = LCB_WIDX(1u), a2 = LCB_WIDX(2u), a3 = LCB_WIDX(3u), a4 = LCB_WIDX(4u), a5 = LCB_WIDX(5u), a6 = LCB_WIDX(6u), a7 = LCB_WIDX(7u);
-#undef LCB_WIDX
-        if (S.U.tab) {
-            const auto tab = LCB_GLOBAL_U32(S.U.tab);
-            const uint32_t o0 = tab[a0 >> LCB_PAGE_SHIFT], o1 = tab[a1 >> LCB_PAGE_SHIFT], o2 = tab[a2 >> LCB_PAGE_SHIFT], o3 = tab[a3 >> LCB_PAGE_SHIFT];
-            const uint32_t o4 = tab[a4 >> LCB_PAGE_SHIFT], o5 = tab[a5 >> LCB_PAGE_SHIFT], o6 = tab[a6 >> LCB_PAGE_SHIFT], o7 = tab[a7 >> LCB_PAGE_SHIFT];
-            a0 += o0; a1 += o1; a2 += o2; a3 += o3; a4 += o4; a5 += o5; a6 += o6; a7 += o7;
-        }
-        R.uw0 = S.U.live[a0]; R.uw1 = S.U.live[a1]; R.uw2 = S.U.live[a2]; R.uw3 = S.U.live[a3];
-        R.uw4 = S.U.live[a4]; R.uw5 = S.U.live[a5]; R.uw6 = S.U.live[a6]; R.uw7 = S.U.live[a7];
-    }
+    for (uint32_t k = 0; k < 8; k++) R.uw[k] = 0;
+    if (R.scan) lcb_used_fetch8(S.U, R.fb, R.up, maxW, R.uw);
     return R;
 }
 
@@ -1135,30 +1153,14 @@ __device__ __forceinline__ LcbVoterReq<typename ST::Flat> lcb_voter_request(cons
 template <bool STATS, class ST>
 __device__ __forceinline__ void lcb_voter_resolve(ST& S, LcbVoterReq<typename ST::Flat>& R, uint32_t dm, bool tryUsed, uint32_t& nv, uint32_t& brk)
 {
-    typedef typename ST::Flat Flat;
-    nv = 0; brk = 0;                                           // steps that vote; 1 if a breaking step (used / in the path) follows them
+    nv = 0; brk = 0;                                        // steps that vote; 1 if a breaking step (used / in the path) follows them
     if (R.walks) {
         const uint32_t wv = R.up ? (R.win & 0xFFFFu) : (R.win >> 16);
         uint32_t L = wv > dm ? wv : dm;
         if (L > R.rem) L = R.rem;
         nv = L;
         if (R.scan) {
-            const bool up = R.up;
-            const Flat fb = R.fb;
-            uint32_t uw0 = R.uw0, uw1 = R.uw1, uw2 = R.uw2, uw3 = R.uw3, uw4 = R.uw4, uw5 = R.uw5, uw6 = R.uw6, uw7 = R.uw7;
-            const uint32_t Lu = (!R.positive && !up && L == R.rem) ? L - 1u : L;   // the step onto the chromosome's first position reads no bit on the - strand
-            const uint32_t sh = up ? ((uint32_t)fb & 31u) : 31u - ((uint32_t)fb & 31u);
-            if (!up) { uw0 = LCB_BREV32(uw0); uw1 = LCB_BREV32(uw1); uw2 = LCB_BREV32(uw2); uw3 = LCB_BREV32(uw3); uw4 = LCB_BREV32(uw4); uw5 = LCB_BREV32(uw5); uw6 = LCB_BREV32(uw6); uw7 = LCB_BREV32(uw7); }
-            const uint64_t s0 = (uint64_t)uw0 | ((uint64_t)uw1 << 32), s1 = (uint64_t)uw2 | ((uint64_t)uw3 << 32), s2 = (uint64_t)uw4 | ((uint64_t)uw5 << 32), s3 = (uint64_t)uw6 | ((uint64_t)uw7 << 32);
-            const uint64_t x0 = (s0 >> sh) | ((s1 << 1) << (63u - sh)), x1 = (s1 >> sh) | ((s2 << 1) << (63u - sh)), x2 = (s2 >> sh) | ((s3 << 1) << (63u - sh)), x3 = s3 >> sh;
-            const uint32_t have = 256u - sh;                   // steps whose bit is in x0 .. x3
-            const uint32_t n = Lu < have ? Lu : have;
-            uint32_t first = 0;                                // first used step (1-based), 0 = none
-#define LCB_SCAN64(x, base) if (!first && n > (base)) { const uint32_t c_ = n - (base) < 64u ? n - (base) : 64u; const uint64_t m_ = (x) & (c_ == 64u ? ~0ull : ((1ull << c_) - 1ull)); if (m_) first = (base) + (uint32_t)__ffsll((long long)m_); }
-            LCB_SCAN64(x0, 0u) LCB_SCAN64(x1, 64u) LCB_SCAN64(x2, 128u) LCB_SCAN64(x3, 192u)
-#undef LCB_SCAN64
-            for (uint32_t d = have + 1; !first && d <= Lu; d++)    // (windows of more than 225 steps: -b beyond 225)
-                if (lcb_used_bit(S.U, (Flat)(up ? fb + (d - 1u) : fb - (d - 1u)))) first = d;
+            const uint32_t first = lcb_used_first(S.U, R.uw, R.fb, R.up, R.positive, L, R.rem);
             if (first) { nv = first - 1u; brk = 1u; }
         }
     }
@@ -1173,7 +1175,7 @@ __device__ __forceinline__ void lcb_voter_resolve(ST& S, LcbVoterReq<typename ST
 }
 
 // ---- The heavy vote of the 16-wavefront variants: wave 0 resolves the voters BEFORE it wakes the helpers, everybody deals items.
-// With tickets over the touch list (lcb_vote_walk_v1) every chunk of a window is its own round trip: fields of the voter, then
+// With tickets over the touch list (lcb_vote_walk_tickets) every chunk of a window is its own round trip: fields of the voter, then
 // posPos / posId / the `used` word of 64 steps, consumed before the next chunk is requested - 0.9-1.0 us per chunk, 70-93 chunks in a
 // config-3 vote of 30-37 voters (profiles/r06). Here wave 0 runs stage A of the compact walk over the whole touch list (lanes =
 // entries, one round trip for all voters) while the helpers still sleep at barrier A, and leaves in LDS
@@ -1182,13 +1184,10 @@ __device__ __forceinline__ void lcb_voter_resolve(ST& S, LcbVoterReq<typename ST
 // After barrier A every wavefront draws LCB_VB items at a time from the ticket counter; an item is ONE load per lane (the id of step
 // chunk * 64 + lane + 1 <= nv) and the hash insert. No barrier is added, and no item touches another wavefront's voter: the pass
 // walks WITHOUT path stops and is verified afterwards (lcb_vote_any_in_path; the wide variant's path set is in LDS), and a hit or
-// an overflow repeats the vote with exact = true, i.e. with lcb_vote_walk_v1, as the variants behind a Bloom filter always did.
-// Which variants: bit m of LCB_VOTE_RESOLVE_MODES (wide and big only - the compact variant has its own walk, the huge one keeps v1);
+// an overflow repeats the vote with exact = true, i.e. with lcb_vote_walk_tickets, as the variants behind a Bloom filter always did.
+// Which variants: LcbCfg<MODE>::RESOLVE (wide and big - the compact variants have their own walk, the huge one keeps the ticket walk);
 // which votes: LCB_VOTE_RESOLVE_MIN <= voters <= LCB_VOTE_RESOLVE_MAX in workgroups of more than two wavefronts. The k = 25 shapes
 // (14 voters of one chunk each) stay below the minimum: resolving first is a loss there (profiles/r06).
-#ifndef LCB_VOTE_RESOLVE_MODES
-#define LCB_VOTE_RESOLVE_MODES 0x6u
-#endif
 #ifndef LCB_VOTE_RESOLVE_MIN
 #define LCB_VOTE_RESOLVE_MIN 24u       // = LCB_VOTE_SHARE_MIN: exactly the votes that share the reduction
 #endif
@@ -1198,7 +1197,7 @@ __device__ __forceinline__ void lcb_voter_resolve(ST& S, LcbVoterReq<typename ST
 #ifndef LCB_VOTE_RESOLVE_ITEMS
 #define LCB_VOTE_RESOLVE_ITEMS 2048u   // items in LDS (4 B each); a vote with more runs today's walk
 #endif
-#define LCB_VOTE_RESOLVE_OF(MODE, NW) ((NW) > 2 && ((MODE) == 1 || (MODE) == 2) && (((LCB_VOTE_RESOLVE_MODES) >> (MODE)) & 1u) != 0)
+#define LCB_VOTE_RESOLVE_OF(MODE, NW) ((NW) > 2 && LcbCfg<(MODE)>::RESOLVE)
 static_assert(LCB_VOTE_RESOLVE_MIN >= 2u && LCB_VOTE_RESOLVE_MAX <= 65536u, "a resolved vote wakes the helpers; a record index has 16 bits");
 // (emulator tests only, -DLCB_TEST_RESOLVE_EVENT=<function>: what the resolved votes of an input went through)
 enum { LCB_RV_RESOLVED = 0, LCB_RV_CHUNK1, LCB_RV_USED_BEYOND_64, LCB_RV_REPEAT_HIT, LCB_RV_ABOVE_MAX, LCB_RV_ITEMS_FULL, LCB_RV_ROUND2, LCB_RV_COUNT };
@@ -1242,7 +1241,7 @@ __device__ inline uint32_t lcb_vote_resolve(ST& S, bool forward, bool tryUsed, b
     const uint32_t maxW = (uint32_t)(S.T.nPos >> 5);             // (the bitmap has at least nPos / 32 + 2 words)
     uint32_t nRec = 0, nItems = 0;
     for (uint32_t p0 = 0; p0 < nTouch; p0 += 64) {
-        LCB_NO_LOADS_IN_FLIGHT();                                  // (see lcb_vote_walk)
+        LCB_NO_LOADS_IN_FLIGHT();                                  // (see lcb_vote_walk_windows)
         LcbVoterReq<Flat> R = lcb_voter_request(S, p0 + S.lane, nTouch, forward, tryUsed, useGood, maxW);
         uint32_t nv, brk;
         lcb_voter_resolve<STATS>(S, R, dm, tryUsed, nv, brk);
@@ -1304,23 +1303,7 @@ __device__ inline void lcb_vote_items(ST& S, bool forward, uint32_t nItems)
                 const uint32_t w1 = lcb_rl(itF[q], 1), wgt = lcb_rl(itF[q], 2), e = lcb_rl(itF[q], 3);
                 const uint32_t d = itC[q] * 64 + S.lane + 1;
                 const int32_t vid = (w1 & 0x10000u) ? itId[q] : -itId[q];
-                if (d <= (w1 & 0xFFFFu)) {
-                    uint32_t h = lcb_hash(vid, S.voteShift);
-                    int32_t old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
-                    uint32_t probe = 0;
-                    while (old != LCB_EMPTY_KEY && old != vid && probe < S.voteCap) {
-                        h = (h + 1) & vmask; probe++;
-                        old = atomicCAS(&S.vKey[h], LCB_EMPTY_KEY, vid);
-                    }
-                    if (old == LCB_EMPTY_KEY) {
-                        const uint32_t tt = atomicAdd(S.vNClaimed, 1u);
-                        if (tt < claimCap) S.vTouched[tt] = (typename ST::Idx)h; else *S.vOvf = 1u;
-                    }
-                    if (old == LCB_EMPTY_KEY || old == vid) {
-                        atomicAdd(&S.vCount[h], wgt);
-                        atomicMax(&S.vLast[h], ((typename ST::VLast)e << ST::LAST_SHIFT) | d);
-                    } else *S.vOvf = 1u;
-                }
+                if (d <= (w1 & 0xFFFFu)) lcb_vote_add(S, vmask, claimCap, vid, wgt, e, d);
             }
         }
     }
@@ -1377,6 +1360,9 @@ __device__ inline LcbBest lcb_vote_argmax(const ST& S, bool forward, bool useGoo
 // Mailbox words through which wave 0 hands a vote to the helper wavefronts of its workgroup.
 enum { LCB_MAIL_CMD = 0, LCB_MAIL_FLAGS, LCB_MAIL_NLIST, LCB_MAIL_FLANK, LCB_MAIL_NTOUCH, LCB_MAIL_FPSPLIT, LCB_MAIL_FPSHIFT, LCB_MAIL_NITEMS, LCB_MAIL_WORDS = 8 };
 enum { LCB_CMD_VOTE = 1, LCB_CMD_EXIT = 2 };
+// LCB_MAIL_FLAGS, the vote as the helpers have to run it: direction, second attempt (used positions allowed), voting list = good list,
+// reduction and clearing shared (barriers C and D), walks stop at path vertices, items of a resolved vote instead of voters
+enum { LCB_VF_FORWARD = 1u, LCB_VF_TRYUSED = 2u, LCB_VF_USEGOOD = 4u, LCB_VF_SHARE = 8u, LCB_VF_EXACT = 16u, LCB_VF_RESOLVED = 32u };
 
 // Clears the vote-table slots named by the entries [s0, s1) of the touched list (blocksfinder.h:761-766).
 template <class ST>
@@ -1392,15 +1378,21 @@ __device__ inline void lcb_vote_clear(ST& S, uint32_t s0, uint32_t s1)
 #define LCB_VOTE_SHARE_MIN 24u         // (the emulator tests also build with a tiny threshold to walk the shared path)
 #endif
 
-// One wave's share of a large vote after the walks: partial arg-max over its slice of the touched list, then (after
-// everyone has read) the clearing of that slice.
+// One wave's part of a vote after the walks, in two halves. First: the arg-max over its slice [s0, s1) of the touched list - the
+// waveId-th of NW equal slices when the reduction is shared, else (wave 0 alone) the whole list.
 template <int NW, class ST>
-__device__ inline void lcb_vote_reduce_slice(ST& S, bool forward, bool useGood, uint32_t waveId, uint32_t nTouched, bool exact)
+__device__ __forceinline__ LcbBest lcb_vote_read_slice(const ST& S, bool forward, bool useGood, bool share, uint32_t waveId, uint32_t nTouched, bool exact,
+                                                       uint32_t& s0, uint32_t& s1, bool& hit)
 {
-    const uint32_t per = (nTouched + NW - 1) / NW;
-    const uint32_t s0 = waveId * per < nTouched ? waveId * per : nTouched, s1 = s0 + per < nTouched ? s0 + per : nTouched;
-    const bool hit = !exact && lcb_vote_any_in_path(S, s0, s1);      // a pass without path stops: is a vertex of this slice in the path?
-    const LcbBest b = lcb_vote_argmax(S, forward, useGood, s0, s1);
+    const uint32_t per = share ? (nTouched + NW - 1) / NW : nTouched;
+    s0 = waveId * per < nTouched ? waveId * per : nTouched; s1 = s0 + per < nTouched ? s0 + per : nTouched;
+    hit = !exact && lcb_vote_any_in_path(S, s0, s1);            // a pass without path stops: is a vertex of this slice in the path?
+    return lcb_vote_argmax(S, forward, useGood, s0, s1);
+}
+// Second, shared votes only: the partial result goes to S.part and (after everyone has read) the slice is cleared.
+template <class ST>
+__device__ __forceinline__ void lcb_vote_publish_slice(ST& S, uint32_t waveId, const LcbBest& b, bool hit, uint32_t s0, uint32_t s1)
+{
     if (S.lane == 0) {
         uint32_t* p = S.part + 8 * waveId;
         p[0] = b.cnt; p[1] = b.keyHi; p[2] = b.keyLo; p[3] = (uint32_t)b.vid; p[4] = b.e; p[5] = hit ? 1u : 0u;
@@ -1409,9 +1401,21 @@ __device__ inline void lcb_vote_reduce_slice(ST& S, bool forward, bool useGood, 
     lcb_vote_clear(S, s0, s1);
     __syncthreads();                                           // D: the table is clean before wave 0 votes again (possibly on its own)
 }
+// (a helper's share of a large vote: both halves)
+template <int NW, class ST>
+__device__ inline void lcb_vote_reduce_slice(ST& S, bool forward, bool useGood, uint32_t waveId, uint32_t nTouched, bool exact)
+{
+    uint32_t s0, s1;
+    bool hit;
+    const LcbBest b = lcb_vote_read_slice<NW>(S, forward, useGood, true, waveId, nTouched, exact, s0, s1, hit);
+    lcb_vote_publish_slice(S, waveId, b, hit, s0, s1);
+}
 
 // One pass of a vote over the voters of the touch list: walks, arg-max, clearing of the table. `hit`: the pass walked without
 // path stops and one of the vertices it touched is in the path (or the touched list is incomplete) - its result is void.
+// A shared vote is the same sequence for every wavefront (wave 0 here, the helpers in lcb_process_body): A - walk (voters or items
+// into the vote table) - B - read the own slice of the touched list (path check, arg-max), write the partial - C - clear the slice - D.
+// Wave 0 alone then reduces the NW partials. A vote that is not shared ends for the helpers at B; wave 0 reads and clears the whole list.
 // (One call site of the walk and one of the arg-max: the compiler inlines everything into the kernel, and until round 5 a vote's code
 // existed thirteen times per instantiation.)
 template <bool STATS, int NW, bool PROF = false, class ST>
@@ -1440,11 +1444,12 @@ __device__ inline LcbBest lcb_vote_pass(ST& S, bool forward, bool tryUsed, bool 
     if (multi) {
         // wake the helper wavefronts: every wave walks its share of the voters
         if (S.lane == 0) {
-            S.mail[LCB_MAIL_FLAGS] = (forward ? 1u : 0u) | (tryUsed ? 2u : 0u) | (useGood ? 4u : 0u) | (share ? 8u : 0u) | (exact ? 16u : 0u) | (resolve ? 32u : 0u);
+            S.mail[LCB_MAIL_FLAGS] = (forward ? LCB_VF_FORWARD : 0u) | (tryUsed ? LCB_VF_TRYUSED : 0u) | (useGood ? LCB_VF_USEGOOD : 0u) | (share ? LCB_VF_SHARE : 0u) |
+                                     (exact ? LCB_VF_EXACT : 0u) | (resolve ? LCB_VF_RESOLVED : 0u);
             S.mail[LCB_MAIL_NTOUCH] = S.nTouch;
             S.mail[LCB_MAIL_FPSPLIT] = S.fpSplit; S.mail[LCB_MAIL_FPSHIFT] = S.fpShift;
             S.mail[LCB_MAIL_NITEMS] = nItems;
-            if (!LCB_WALK_V2_OF(ST) || resolve) *S.vTicket = 0;
+            if (!LcbCfg<ST::MODE>::WINDOW_WALK || resolve) *S.vTicket = 0;
             S.mail[LCB_MAIL_CMD] = LCB_CMD_VOTE;
         }
         __syncthreads();                                           // A
@@ -1460,19 +1465,11 @@ __device__ inline LcbBest lcb_vote_pass(ST& S, bool forward, bool tryUsed, bool 
     uint32_t nTouched = lcb_rfl(*S.vNClaimed);
     if (nTouched > claimCap) nTouched = claimCap;
     if (STATS && multi && S.lane == 0) { S.cWalk += *S.mailWalk; *S.mailWalk = 0; }
-    // wave 0's slice of the touched list: all of it unless the reduction is shared
-    const uint32_t per = share ? (nTouched + NW - 1) / NW : nTouched;
-    const uint32_t s1 = per < nTouched ? per : nTouched;
-    hit = !exact && lcb_vote_any_in_path(S, 0, s1);               // a pass without path stops: is a vertex of this slice in the path?
-    b = lcb_vote_argmax(S, forward, useGood, 0, s1);
+    // wave 0's slice of the touched list, like everyone's: all of it unless the reduction is shared
+    uint32_t s0, s1;
+    b = lcb_vote_read_slice<NW>(S, forward, useGood, share, 0, nTouched, exact, s0, s1, hit);
     if (share) {
-        if (S.lane == 0) {
-            uint32_t* p = S.part;
-            p[0] = b.cnt; p[1] = b.keyHi; p[2] = b.keyLo; p[3] = (uint32_t)b.vid; p[4] = b.e; p[5] = hit ? 1u : 0u;
-        }
-        __syncthreads();                                           // C: every slice has been read, partials are visible
-        lcb_vote_clear(S, 0, s1);
-        __syncthreads();                                           // D: the table is clean before wave 0 votes again (possibly on its own)
+        lcb_vote_publish_slice(S, 0, b, hit, s0, s1);              // contains barriers C and D
         // final reduction over the NW partial results
         uint32_t pc = 0, ph = 0xFFFFFFFFu, pl = 0xFFFFFFFFu, pv = 0, pe = 0, pHit = 0;
         if (S.lane < (uint32_t)NW) { const uint32_t* p = S.part + 8 * S.lane; pc = p[0]; ph = p[1]; pl = p[2]; pv = p[3]; pe = p[4]; pHit = p[5]; }
@@ -1487,7 +1484,7 @@ __device__ inline LcbBest lcb_vote_pass(ST& S, bool forward, bool tryUsed, bool 
         b.e = lcb_rl(pe, w);
     } else {
         LCB_SYNC_IF(LcbCfg<ST::MODE>::IDX_LDS);
-        lcb_vote_clear(S, 0, s1);
+        lcb_vote_clear(S, s0, s1);
     }
     if (PROF && !LCB_PROF_PUSH) S.pfTReduce += wall_clock64() - tw2;
     ovfAny = lcb_rfl(*S.vOvf) != 0;
@@ -2308,19 +2305,19 @@ __device__ inline void lcb_process_body(const LcbTables& T, const LcbKParams& P,
                 S.nTouch = lcb_rfl(S.mail[LCB_MAIL_NTOUCH]);
                 S.fpSplit = lcb_rfl(S.mail[LCB_MAIL_FPSPLIT]); S.fpShift = lcb_rfl(S.mail[LCB_MAIL_FPSHIFT]);
                 S.cWalk = 0;
-                if (RESOLVE && (flags & 32u)) lcb_vote_items<false>(S, (flags & 1u) != 0, lcb_rfl(S.mail[LCB_MAIL_NITEMS]));   // a resolved vote: items, not voters
-                else lcb_vote_walk<STATS>(S, (flags & 1u) != 0, (flags & 2u) != 0, (flags & 4u) != 0, waveId, NW, (flags & 16u) != 0);
+                if (RESOLVE && (flags & LCB_VF_RESOLVED)) lcb_vote_items<false>(S, (flags & LCB_VF_FORWARD) != 0, lcb_rfl(S.mail[LCB_MAIL_NITEMS]));   // a resolved vote: items, not voters
+                else lcb_vote_walk<STATS>(S, (flags & LCB_VF_FORWARD) != 0, (flags & LCB_VF_TRYUSED) != 0, (flags & LCB_VF_USEGOOD) != 0, waveId, NW, (flags & LCB_VF_EXACT) != 0);
                 if (STATS) {
                     const unsigned long long w = (unsigned long long)lcb_wave_sum((int64_t)S.cWalk);
                     if (S.lane == 0 && w) atomicAdd(S.mailWalk, w);
                 }
                 __syncthreads();                                   // B
-                if (flags & 8u) {
+                if (flags & LCB_VF_SHARE) {
                     // a vote with many voters is reduced and cleared by everyone (wave 0 resets the counter only after barrier D)
                     uint32_t nTouched = lcb_rfl(*S.vNClaimed);
                     const uint32_t claimCap = S.voteCap - (S.voteCap >> 2);
                     if (nTouched > claimCap) nTouched = claimCap;
-                    lcb_vote_reduce_slice<NW>(S, (flags & 1u) != 0, (flags & 4u) != 0, waveId, nTouched, (flags & 16u) != 0);   // contains barriers C and D
+                    lcb_vote_reduce_slice<NW>(S, (flags & LCB_VF_FORWARD) != 0, (flags & LCB_VF_USEGOOD) != 0, waveId, nTouched, (flags & LCB_VF_EXACT) != 0);   // contains barriers C and D
                 }
             }
         }
