@@ -1,5 +1,5 @@
-// device.hip — HBM residency, workspaces and launches for the gfx950 block-finder kernels, plus the
-// single-GPU phase loop (BlocksFinder::FindBlocks, blocksfinder.h:453-530).
+// device.hip — HBM residency, workspaces and launches for the gfx950 block-finder kernels: one device's tables, `used` bitmap and
+// views, its synchronous, overlapped and side-lane launches, and the LcbProcessor the round engine (engine.cpp) drives them through.
 //
 // Data layout in HBM (one copy per GPU, read-only except `used`):
 //   chrLoHi uint2[C] | segBase u64[32] | posId i32[P] | posPos u32[P] | posCh u8[P] | posRevCh u8[P]
@@ -27,11 +27,13 @@
 #include <iostream>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include "lcb_device.h"
 #include "lcb_kernel.h"
+#include "lcb_owned.h"
 #include "lcb_segments.h"
 
 #define HIP_CHECK(x)                                                                              \
@@ -163,6 +165,57 @@ uint32_t envU32(const char* name, uint32_t dflt)
 
 const char* modeName(int m) { return m == 3 ? "huge" : (m == 2 ? "big" : (m == 1 ? "wide" : "compact")); }
 
+// Every instantiation of the process kernel that exists: [mode 0..4 (4: the compact variant with the small pools)][flavour][seg].
+using ProcessKernel = void (*)(LcbTables, LcbKParams, const LcbKSeed*, uint32_t, LcbWork, LcbSeedOut*, uint4*, unsigned long long, LcbFpOut*, unsigned long long);
+enum Flavour { FLAVOUR_PLAIN = 0, FLAVOUR_STATS = 1, FLAVOUR_PROF = 2 };
+struct ProcessVariant { ProcessKernel kernel[3][2]; int nw; };
+template <int MODE, int NW>
+constexpr ProcessVariant processVariant()
+{
+    return ProcessVariant{{{lcb_process_kernel<MODE, false, NW, false, false>, lcb_process_kernel<MODE, false, NW, false, true>},
+                           {lcb_process_kernel<MODE, true, NW, false, false>, lcb_process_kernel<MODE, true, NW, false, true>},
+                           {lcb_process_kernel<MODE, false, NW, true, false>, lcb_process_kernel<MODE, false, NW, true, true>}}, NW};
+}
+const ProcessVariant kProcessVariants[5] = {processVariant<0, LCB_NW_COMPACT>(), processVariant<1, LCB_NW_WIDE>(), processVariant<2, LCB_NW_BIG>(),
+                                            processVariant<3, LCB_NW_HUGE>(), processVariant<4, LCB_NW_COMPACT>()};
+
+// What a launch reads its seeds from and writes its results to (pinned, device-mapped host memory); fp null: no footprints.
+struct LaunchIo { const LcbKSeed* seeds; uint32_t nSeeds; LcbSeedOut* out; uint4* arena; unsigned long long arenaCap; LcbFpOut* fp; unsigned long long fpCap; };
+
+// THE launch of a process kernel: `grid` workgroups of the instantiation (mode, flavour, seg) on stream q.
+void launchProcess(int mode, Flavour flavour, bool seg, uint32_t grid, hipStream_t q, const LcbTables& T, const LcbKParams& KP, const LcbWork& W, const LaunchIo& io)
+{
+    const ProcessVariant& v = kProcessVariants[mode];
+    hipLaunchKernelGGL(v.kernel[flavour][seg ? 1 : 0], dim3(grid), dim3(64 * v.nw), 0, q, T, KP, io.seeds, io.nSeeds, W, io.out, io.arena, io.arenaCap, io.fp, io.fpCap);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The workspace and work queue of one launch: the slots of w; of the control words ctl [ticketWord] hands out the tickets, [2..3] is
+// the arena allocator and [4..5] the footprint allocator; tickets (with their number in *nTickets) maps a ticket to a seed, or null.
+LcbWork makeWork(const WorkSet& w, uint32_t* ctl, uint32_t ticketWord, const uint32_t* tickets, const uint32_t* nTickets, const uint32_t* abort, LcbSeedCtr* ctr, uint32_t* dbg)
+{
+    LcbWork W;
+    W.base = w.base; W.slotBytes = w.slotBytes; W.pathCap = w.pathCap; W.bodyCap = w.bodyCap; W.bestCap = w.bestCap; W.instCap = w.instCap; W.voteCap = w.voteCap;
+    W.cursor = ctl + ticketWord; W.cursorBase = 0; W.live = tickets; W.nLive = nTickets;
+    W.arenaCursor = (unsigned long long*)(ctl + 2); W.arenaBase = 0; W.fpCursor = (unsigned long long*)(ctl + 4); W.fpBase = 0;
+    W.ctr = ctr; W.dbg = dbg; W.abort = abort;
+    return W;
+}
+
+int releaseHip(LcbOwnedKind kind, void* p)
+{
+    return (int)(kind == LCB_OWN_DEVICE ? hipFree(p) : kind == LCB_OWN_PINNED ? hipHostFree(p) : kind == LCB_OWN_STREAM ? hipStreamDestroy((hipStream_t)p) : hipEventDestroy((hipEvent_t)p));
+}
+
+// One set of the host buffers of the synchronous launches with the events around its kernels. A device has two: calls run on the
+// first; the second is for the launch that runs while the host is still busy with the previous round (processBegin / processEnd).
+struct HostBufs {
+    LcbKSeed* seeds = nullptr; LcbSeedOut* out = nullptr; uint4* arena = nullptr; LcbFpOut* fp = nullptr;     // (fp: the footprint arena)
+    uint32_t* live = nullptr;                    // ticket -> seed index of a screened launch, copied from the device, [batchCap + 1]: the last word is their number
+    unsigned long long arenaCap = 0, fpCap = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;       // [e0, e1]: screening + process kernel
+};
+
 }  // namespace
 
 // The predicted views of one launch: a page table per view and a pool of private pages behind the live bitmap.
@@ -195,8 +248,8 @@ struct SideLane {
 
 struct lcb_device_impl {
     int ordinal = 0;
+    LcbOwner own{releaseHip};                    // every allocation, stream and event below, the lanes' included: destroy releases what is registered here
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const lcb_graph* g = nullptr;
     lcb_params p{};
     lcb_device_opts o{};
@@ -204,7 +257,6 @@ struct lcb_device_impl {
     LcbKParams KP{};
     LcbSegPlan plan;                             // host positions <-> (segment, g) of the device tables
     bool seg = false;                            // the SEG instantiations of the kernels run (several segments)
-    std::vector<void*> owned;
     uint32_t* dUsed = nullptr;                   // the live bitmap
     size_t usedWords = 0;                        // its words (a multiple of the page size)
     uint32_t nPages = 0;
@@ -217,25 +269,10 @@ struct lcb_device_impl {
     struct lcb_async_call* async = nullptr;      // the call begun with processBegin and not yet ended
     uint32_t* dCursor = nullptr;                 // [0] work tickets, [1] live seeds, [2..3] arena allocator (u64), [4..5] footprint allocator (u64)
     uint32_t* dLive = nullptr;                   // ticket -> seed index of a screened launch
-    uint32_t* hLive = nullptr;                   // ... copied to the host after the launch, [batchCap + 1]: the last word is their number
     WorkSet ws[4];                               // compact, wide, big, huge
-    // pinned, device-mapped host buffers
-    LcbKSeed* hSeeds = nullptr;
-    LcbSeedOut* hOut = nullptr;
-    LcbSeedCtr* hCtr = nullptr;                  // stats / instrumented variants only
-    uint4* hArena = nullptr;
-    LcbFpOut* hFp = nullptr;                     // footprint arena (pinned)
-    unsigned long long fpCap = 0;
+    HostBufs bufs, bufsEarly;                    // pinned, device-mapped host buffers: of the calls, of the overlapped launch
+    LcbSeedCtr* hCtr = nullptr;                  // pinned; stats / instrumented variants only (never the overlapped launch)
     LcbMarkRange* hRanges = nullptr;
-    // second set of the host buffers, for the launch that runs while the host still commits the previous round (processBegin/End)
-    LcbKSeed* hSeedsB = nullptr; LcbSeedOut* hOutB = nullptr; uint4* hArenaB = nullptr; LcbFpOut* hFpB = nullptr; uint32_t* hLiveB = nullptr;
-    unsigned long long arenaCapB = 0, fpCapB = 0;
-    hipEvent_t ev2 = nullptr, ev3 = nullptr;
-    void swapBufs()
-    {
-        std::swap(hSeeds, hSeedsB); std::swap(hOut, hOutB); std::swap(hArena, hArenaB); std::swap(hFp, hFpB); std::swap(hLive, hLiveB);
-        std::swap(arenaCap, arenaCapB); std::swap(fpCap, fpCapB);
-    }
     uint32_t* hDbg = nullptr;                    // flight recorder (LCB_DEBUG=1): 16 words per workgroup
     uint32_t dbgSlots = 0;
     bool forceProf = false;                      // LCB_FORCE_PROF=1: always use the instrumented kernel variants
@@ -243,10 +280,8 @@ struct lcb_device_impl {
     FILE* traceFile = nullptr;                   // LCB_TRACE_LAUNCHES=<file>: one line per launch (seeds, grid, mode, ms)
     double watchdogS = 0;                        // LCB_WATCHDOG_S: abort a launch that runs longer (0 = wait forever)
     uint32_t batchCap = 0;
-    unsigned long long arenaCap = 0;
     uint32_t rangeCap = 0;
     bool stats = false;
-    bool wantFp = false;                         // emit footprints (speculative engine)
     // seeds that overflowed the LDS capacities before: (vid, ch) -> kernel mode to start with next time, so that a
     // recomputation does not repeat the doomed attempt
     std::unordered_map<uint64_t, uint8_t> modeHint;
@@ -265,7 +300,7 @@ struct lcb_device_impl {
     void resetSpans()
     {
         kernelSpans.clear();
-        if (!evBase) HIP_CHECK(hipEventCreate(&evBase));
+        if (!evBase) evBase = newEvent();
         HIP_CHECK(hipEventRecord(evBase, stream));
         HIP_CHECK(hipEventSynchronize(evBase));
     }
@@ -297,14 +332,27 @@ struct lcb_device_impl {
 
     void use() { HIP_CHECK(hipSetDevice(ordinal)); }
 
+    // Everything the device holds is made by one of these four and belongs to `own` from then on; drop() releases a buffer that is
+    // about to be made again in another size.
+    template <class T_>
+    T_* devAlloc(size_t bytes) { return (T_*)own.make(LCB_OWN_DEVICE, [&] { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); return p; }); }
+    template <class T_>
+    T_* pinnedAlloc(size_t bytes, unsigned flags = hipHostMallocDefault) { return (T_*)own.make(LCB_OWN_PINNED, [&] { void* p = nullptr; HIP_CHECK(hipHostMalloc(&p, bytes, flags)); return p; }); }
+    hipStream_t newStream(const int* priority)   // null: no priority asked for
+    {
+        auto make = [&] { hipStream_t s = nullptr; HIP_CHECK(priority ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, *priority) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return (void*)s; };
+        return (hipStream_t)own.make(LCB_OWN_STREAM, make);
+    }
+    hipEvent_t newEvent() { return (hipEvent_t)own.make(LCB_OWN_EVENT, [] { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreate(&e)); return (void*)e; }); }
+    template <class T_>
+    void drop(T_*& p) { T_* q = p; p = nullptr; HIP_CHECK((hipError_t)own.drop(q)); }
+
     template <class T_>
     T_* upload(const T_* src, size_t n)
     {
-        void* d = nullptr;
-        HIP_CHECK(hipMalloc(&d, (n ? n : 1) * sizeof(T_)));
-        owned.push_back(d);
+        T_* d = devAlloc<T_>((n ? n : 1) * sizeof(T_));
         if (n) HIP_CHECK(hipMemcpy(d, src, n * sizeof(T_), hipMemcpyHostToDevice));
-        return (T_*)d;
+        return d;
     }
 
     // a per-position table: the segments of the host array go to their places in the device's flat index space (contiguous unless a
@@ -312,144 +360,328 @@ struct lcb_device_impl {
     template <class T_>
     T_* uploadSeg(const T_* src, const LcbSegPlan& pl)
     {
-        void* dv = nullptr;
-        HIP_CHECK(hipMalloc(&dv, (size_t)(pl.devPositions ? pl.devPositions : 1) * sizeof(T_)));
-        owned.push_back(dv);
+        T_* dv = devAlloc<T_>((size_t)(pl.devPositions ? pl.devPositions : 1) * sizeof(T_));
         for (uint32_t sg = 0; sg < pl.nSeg(); sg++) {
             const uint64_t a = pl.segStart[sg], b = pl.segStart[sg + 1];
-            if (b > a) HIP_CHECK(hipMemcpy((T_*)dv + pl.segDev[sg], src + a, (size_t)(b - a) * sizeof(T_), hipMemcpyHostToDevice));
+            if (b > a) HIP_CHECK(hipMemcpy(dv + pl.segDev[sg], src + a, (size_t)(b - a) * sizeof(T_), hipMemcpyHostToDevice));
         }
-        return (T_*)dv;
+        return dv;
     }
 
     void allocWork(WorkSet& w)
     {
-        if (w.base) { HIP_CHECK(hipFree(w.base)); w.base = nullptr; }
+        drop(w.base);
         // instCap != 0: instance fields in the slot (big, huge); voteCap != 0: index, lists and vote table too (huge)
         const LcbSlotLayout L = lcb_slot_layout(w.pathCap, w.bodyCap, w.bestCap, w.instCap, w.voteCap);
         w.slotBytes = L.total;
-        HIP_CHECK(hipMalloc((void**)&w.base, (size_t)w.slotBytes * w.nSlots));
+        w.base = devAlloc<uint8_t>((size_t)w.slotBytes * w.nSlots);
         hipLaunchKernelGGL(lcb_init_slots_kernel, dim3(w.nSlots), dim3(256), 0, stream, w.base, w.slotBytes, L, w.pathCap, w.voteCap);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(stream));
     }
 
-    void allocArena(unsigned long long cap)
+    void allocArena(HostBufs& B, unsigned long long cap)
     {
-        if (hArena) HIP_CHECK(hipHostFree(hArena));
-        if (hFp) HIP_CHECK(hipHostFree(hFp));
-        arenaCap = cap; fpCap = cap;
-        HIP_CHECK(hipHostMalloc((void**)&hArena, (size_t)cap * sizeof(uint4), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&hFp, (size_t)cap * sizeof(LcbFpOut), hipHostMallocDefault));
+        drop(B.arena); drop(B.fp);
+        B.arenaCap = cap; B.fpCap = cap;
+        B.arena = pinnedAlloc<uint4>((size_t)cap * sizeof(uint4));
+        B.fp = pinnedAlloc<LcbFpOut>((size_t)cap * sizeof(LcbFpOut));
     }
 
-    // One launch over hSeeds[0..m): optional screening, then the process kernel of w's variant. Returns after the stream
-    // has drained; hOut[0..m) then holds every seed's header. wait = false only enqueues (events evA/evB); finishLaunch()
-    // then waits for it.
-    void launch(WorkSet& w, uint32_t m, bool screen, bool wait = true)
+    bool instrumented() const { return hDbg != nullptr || seedTrace || forceProf; }     // the prof flavour runs (one profile buffer: no overlapped launch, no lanes)
+    static uint32_t gridOf(const WorkSet& w, uint32_t m) { return m < w.nSlots ? m : w.nSlots; }
+    bool recorded(uint32_t grid) const { return hDbg && grid <= dbgSlots; }              // the flight recorder is on in a launch of that many workgroups
+
+    // Enqueues one launch over B.seeds[0..m): optional screening, then the process kernel of w's variant, between the events of B.
+    // finishLaunch() waits for it; B.out[0..m) then holds every seed's header.
+    void launch(WorkSet& w, HostBufs& B, uint32_t m, bool screen, bool wantFp)
     {
-        hipEvent_t evA = wait ? ev0 : ev2, evB = wait ? ev1 : ev3;
-        LcbWork W;
-        W.base = w.base; W.slotBytes = w.slotBytes; W.pathCap = w.pathCap; W.bodyCap = w.bodyCap; W.bestCap = w.bestCap;
-        W.instCap = w.instCap; W.voteCap = w.voteCap;
-        W.cursor = dCursor; W.cursorBase = 0;
-        W.live = screen ? dLive : nullptr; W.nLive = screen ? dCursor + 1 : nullptr;
-        W.arenaCursor = (unsigned long long*)(dCursor + 2); W.arenaBase = 0;
-        W.fpCursor = (unsigned long long*)(dCursor + 4); W.fpBase = 0;
-        const bool prof = (hDbg != nullptr) || seedTrace || forceProf;
-        W.ctr = (stats || prof) ? hCtr : nullptr;
-        const uint32_t grid = m < w.nSlots ? m : w.nSlots;
-        W.dbg = (hDbg && grid <= dbgSlots) ? hDbg : nullptr;
-        W.abort = nullptr;
+        const bool prof = instrumented();
+        const uint32_t grid = gridOf(w, m);
+        const LcbWork W = makeWork(w, dCursor, 0, screen ? dLive : nullptr, screen ? dCursor + 1 : nullptr, nullptr, (stats || prof) ? hCtr : nullptr, recorded(grid) ? hDbg : nullptr);
         if (W.dbg) memset(hDbg, 0, (size_t)grid * 16 * sizeof(uint32_t));
         if (W.ctr && !stats) memset(hCtr, 0, (size_t)m * sizeof(LcbSeedCtr));   // screened-out seeds write no profile
-        if (watchdogS > 0 || screen) for (uint32_t i = 0; i < m; i++) hOut[i].status = LCB_ST_PENDING;   // unfinished seeds can be named (and a header nobody wrote is noticed)
+        if (watchdogS > 0 || screen) for (uint32_t i = 0; i < m; i++) B.out[i].status = LCB_ST_PENDING;   // unfinished seeds can be named (and a header nobody wrote is noticed)
         HIP_CHECK(hipMemsetAsync(dCursor, 0, 32, stream));
-        HIP_CHECK(hipEventRecord(evA, stream));
+        HIP_CHECK(hipEventRecord(B.e0, stream));
         if (screen) {
-            hipLaunchKernelGGL(lcb_screen_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, T, hSeeds, m, hOut, dLive, dCursor + 1);
+            hipLaunchKernelGGL(lcb_screen_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, T, B.seeds, m, B.out, dLive, dCursor + 1);
             HIP_CHECK(hipGetLastError());
         }
-#define LCB_NW(MODE) (MODE == 3 ? LCB_NW_HUGE : (MODE == 2 ? LCB_NW_BIG : (MODE == 1 ? LCB_NW_WIDE : LCB_NW_COMPACT)))     /* (0 and 4: the compact variant) */
-#define LCB_LAUNCH(MODE, ST, PF, SG) hipLaunchKernelGGL((lcb_process_kernel<MODE, ST, LCB_NW(MODE), PF, SG>), dim3(grid), dim3(64 * LCB_NW(MODE)), 0, stream, \
-                                                  T, KP, hSeeds, m, W, hOut, hArena, arenaCap, wantFp ? hFp : nullptr, fpCap)
-#define LCB_LAUNCH_SEG(MODE, ST, PF) do { if (seg) LCB_LAUNCH(MODE, ST, PF, true); else LCB_LAUNCH(MODE, ST, PF, false); } while (0)
-#define LCB_LAUNCH_MODE(MODE) do { if (stats) LCB_LAUNCH_SEG(MODE, true, false); else if (prof) LCB_LAUNCH_SEG(MODE, false, true); else LCB_LAUNCH_SEG(MODE, false, false); } while (0)
-        if (w.mode == 3) LCB_LAUNCH_MODE(3);
-        else if (w.mode == 2) LCB_LAUNCH_MODE(2);
-        else if (w.mode == 1) LCB_LAUNCH_MODE(1);
-        else if (compactSmall) LCB_LAUNCH_MODE(4);
-        else LCB_LAUNCH_MODE(0);
-#undef LCB_LAUNCH_MODE
-#undef LCB_LAUNCH_SEG
-#undef LCB_LAUNCH
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(evB, stream));       // [evA, evB]: screening + process kernel
+        launchProcess(w.mode == 0 && compactSmall ? 4 : w.mode, stats ? FLAVOUR_STATS : (prof ? FLAVOUR_PROF : FLAVOUR_PLAIN), seg, grid, stream, T, KP, W,
+                      LaunchIo{B.seeds, m, B.out, B.arena, B.arenaCap, wantFp ? B.fp : nullptr, B.fpCap});
+        HIP_CHECK(hipEventRecord(B.e1, stream));
         if (screen) {      // the host only looks at the seeds that survived the screening
-            HIP_CHECK(hipMemcpyAsync(hLive + batchCap, dCursor + 1, 4, hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(hLive, dLive, (size_t)m * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(B.live + batchCap, dCursor + 1, 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(B.live, dLive, (size_t)m * 4, hipMemcpyDeviceToHost, stream));
         }
-        if (!wait) return;
-        finishLaunch(w, m, grid, W.dbg != nullptr, evA, evB);
     }
 
-    void finishLaunch(WorkSet& w, uint32_t m, uint32_t grid, bool haveDbg, hipEvent_t evA, hipEvent_t evB)
+    // a kernel that does not finish is reported with its unfinished seeds and its flight recorder instead of hanging the caller
+    [[noreturn]] void watchdogExpired(const WorkSet& w, const HostBufs& B, uint32_t m, uint32_t grid, double el)
     {
-        if (watchdogS > 0) {
-            // bounded wait: a kernel that does not finish is reported with its flight recorder instead of hanging the caller
+        fprintf(stderr, "lcb: kernel watchdog: launch of %u seeds (%s mode, grid %u) still running after %.1f s\n", m, modeName(w.mode), grid, el);
+        int shownSeeds = 0;
+        uint32_t unfinished = 0;
+        for (uint32_t i = 0; i < m; i++) if (B.out[i].status == LCB_ST_PENDING) unfinished++;
+        fprintf(stderr, "  %u of %u seeds unfinished; first ones:", unfinished, m);
+        for (uint32_t i = 0; i < m && shownSeeds < 8; i++)
+            if (B.out[i].status == LCB_ST_PENDING) { fprintf(stderr, " [%u] vid=%d ch=%d", i, B.seeds[i].vid, B.seeds[i].ch); shownSeeds++; }
+        fprintf(stderr, "\n");
+        if (recorded(grid)) {
+            int shown = 0;
+            for (uint32_t b = 0; b < grid && shown < 8; b++) {
+                const uint32_t* r = hDbg + 16 * b;
+                if (r[0] == 2) continue;
+                shown++;
+                fprintf(stderr, "  wg %u: state=%u seed=%u stage=%u nInst=%u nRight=%u nLeft=%u ext=%u next=%d g=%u\n", b, r[0], r[1], r[2], r[3], r[4], r[5], r[6], (int)r[7], r[8]);
+            }
+        }
+        fflush(stderr);
+        throw LcbError("kernel watchdog expired (LCB_WATCHDOG_S)");
+    }
+
+    // The hipEvent-timed duration of the kernels between e0 and e1 (both reached) goes into the totals; side: a lane's kernel.
+    float accountKernel(int mode, hipEvent_t e0, hipEvent_t e1, bool side)
+    {
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        kernelMs += ms; launches++; modeMs[mode] += ms; modeLaunches[mode]++;
+        if (side) sideKernelMs += ms;
+        noteSpan(e0, e1);
+        return ms;
+    }
+
+    // one line per launch and, with LCB_TRACE_SEEDS, the profile of its slowest seeds (ticks are 10 ns)
+    void traceLaunch(const WorkSet& w, const HostBufs& B, uint32_t m, uint32_t grid, float ms)
+    {
+        static const char* const names[15] = {"ticks", "push", "vote", "probe", "inst", "tv", "tp", "ts", "cwalk", "cwaitb", "creduce", "cscan", "voters", "chunks", "touch"};
+        fprintf(traceFile, "%lld\t%u\t%u\t%s\t%.4f\n", (long long)launches, m, grid, modeName(w.mode), ms);
+        if (stats || !seedTrace || !hCtr) return;
+        for (uint32_t i = 0; i < m; i++) {
+            if (hCtr[i].c[0] <= 2000) continue;
+            fprintf(traceFile, "#seed\t%lld\t%u\t%d\tst=%u\tn=%u", (long long)launches, i, B.seeds[i].vid, B.out[i].status, B.out[i].nInst);
+            for (int j = 0; j < 15; j++) fprintf(traceFile, "\t%s=%llu", names[j], (unsigned long long)hCtr[i].c[j]);
+            fputc('\n', traceFile);
+        }
+    }
+
+    void finishLaunch(WorkSet& w, HostBufs& B, uint32_t m)
+    {
+        const uint32_t grid = gridOf(w, m);
+        if (watchdogS > 0) {      // bounded wait
             const auto t0 = std::chrono::steady_clock::now();
             for (;;) {
-                const hipError_t q = hipEventQuery(evB);
+                const hipError_t q = hipEventQuery(B.e1);
                 if (q == hipSuccess) break;
                 if (q != hipErrorNotReady) HIP_CHECK(q);
                 const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                if (el > watchdogS) {
-                    fprintf(stderr, "lcb: kernel watchdog: launch of %u seeds (%s mode, grid %u) still running after %.1f s\n", m, modeName(w.mode), grid, el);
-                    {
-                        int shownSeeds = 0;
-                        uint32_t unfinished = 0;
-                        for (uint32_t i = 0; i < m; i++) if (hOut[i].status == LCB_ST_PENDING) unfinished++;
-                        fprintf(stderr, "  %u of %u seeds unfinished; first ones:", unfinished, m);
-                        for (uint32_t i = 0; i < m && shownSeeds < 8; i++)
-                            if (hOut[i].status == LCB_ST_PENDING) { fprintf(stderr, " [%u] vid=%d ch=%d", i, hSeeds[i].vid, hSeeds[i].ch); shownSeeds++; }
-                        fprintf(stderr, "\n");
-                    }
-                    if (haveDbg) {
-                        int shown = 0;
-                        for (uint32_t b = 0; b < grid && shown < 8; b++) {
-                            const uint32_t* r = hDbg + 16 * b;
-                            if (r[0] == 2) continue;
-                            shown++;
-                            fprintf(stderr, "  wg %u: state=%u seed=%u stage=%u nInst=%u nRight=%u nLeft=%u ext=%u next=%d g=%u\n", b, r[0], r[1], r[2], r[3], r[4], r[5], r[6], (int)r[7], r[8]);
-                        }
-                    }
-                    fflush(stderr);
-                    throw LcbError("kernel watchdog expired (LCB_WATCHDOG_S)");
-                }
+                if (el > watchdogS) watchdogExpired(w, B, m, grid, el);
                 if (el > 0.002) { struct timespec ts = {0, 200000}; nanosleep(&ts, nullptr); }
             }
         }
         HIP_CHECK(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, evA, evB));
-        kernelMs += ms;
-        launches++;
-        noteSpan(evA, evB);
+        const float ms = accountKernel(w.mode, B.e0, B.e1, false);
         modeSeeds[w.mode] += m;
-        modeMs[w.mode] += ms; modeLaunches[w.mode]++;
-        if (traceFile) {
-            fprintf(traceFile, "%lld\t%u\t%u\t%s\t%.4f\n", (long long)launches, m, grid, modeName(w.mode), ms);
-            if (!stats && seedTrace && hCtr)  // per-seed profile of the slowest seeds of the launch (ticks are 10 ns)
-                for (uint32_t i = 0; i < m; i++)
-                    if (hCtr[i].c[0] > 2000)
-                        fprintf(traceFile, "#seed\t%lld\t%u\t%d\tst=%u\tn=%u\tticks=%llu\tpush=%llu\tvote=%llu\tprobe=%llu\tinst=%llu\ttv=%llu\ttp=%llu\tts=%llu\tcwalk=%llu\tcwaitb=%llu\tcreduce=%llu\tcscan=%llu\tvoters=%llu\tchunks=%llu\ttouch=%llu\n", (long long)launches, i, hSeeds[i].vid,
-                            hOut[i].status, hOut[i].nInst, (unsigned long long)hCtr[i].c[0], (unsigned long long)hCtr[i].c[1], (unsigned long long)hCtr[i].c[2],
-                            (unsigned long long)hCtr[i].c[3], (unsigned long long)hCtr[i].c[4], (unsigned long long)hCtr[i].c[5], (unsigned long long)hCtr[i].c[6],
-                            (unsigned long long)hCtr[i].c[7], (unsigned long long)hCtr[i].c[8], (unsigned long long)hCtr[i].c[9], (unsigned long long)hCtr[i].c[10],
-                            (unsigned long long)hCtr[i].c[11], (unsigned long long)hCtr[i].c[12], (unsigned long long)hCtr[i].c[13], (unsigned long long)hCtr[i].c[14]);
-        }
+        if (traceFile) traceLaunch(w, B, m, grid, ms);
     }
 };
+
+// ---- creation, in the order of its allocations: options, queue, tables, `used` bitmap and views, work sets, host buffers,
+// diagnostics, lanes. Whatever a step makes is registered in d->own as it is made, so a failure anywhere leaves nothing behind.
+namespace {
+
+// option defaults and checks
+void createOptions(lcb_device_impl* d, uint32_t nCu)
+{
+    const lcb_graph* g = d->g;
+    lcb_device_opts& o = d->o;
+    // positions: (segment, g) pairs (lcb_segments.h); seg_cap / seg_gap are test hooks (small segments on small inputs, flat indices
+    // beyond 2^32 through unused table space between the segments)
+    d->plan = lcb_plan_segments(*g, o.seg_cap, o.seg_gap);
+    d->seg = d->plan.nSeg() > 1 || o.seg_cap != 0;
+    // defaults: compact 5 workgroups per CU (LDS-bound; 4 with the segment tables of the SEG kernels), wide 1 per CU, big 1 per CU
+    // the compact variant's pools: small ones where a vertex has few occurrences (paths of few instances: k = 25 inputs of 8-16 genomes, 6-12
+    // occurrences per vertex; the 62-strain shape has 26 at 1/40 of its size and more at full size, and its paths outgrow 128 instances)
+    if (o.compact_pools > 2) throw LcbError("lcb_device_opts.compact_pools: 0 (by the input), 1 (256 instances / 1 024 vote slots) or 2 (128 / 512)");
+    d->compactAuto = o.compact_pools == 0;
+    // (the occurrence-weighted mean of the occurrences per vertex: "the typical occurrence belongs to a vertex with that many" - 6-14 for the k = 25 shapes of 8 / 16
+    // genomes, 35+ for the 62-strain shape, 25 for the 10-strain one, whose many strain-private vertices would hide that in a plain mean)
+    long double occSq = 0;
+    for (size_t v = 0; v + 1 < g->occStart.size(); v++) { const long double nv = (long double)(g->occStart[v + 1] - g->occStart[v]); occSq += nv * nv; }
+    d->compactSmall = o.compact_pools == 2 || (o.compact_pools == 0 && g->nPos() > 0 && occSq <= 20.0L * (long double)g->nPos());
+    d->compactLargeSlots = o.compact_slots ? o.compact_slots : (d->seg ? 4 : 5) * nCu;
+    if (!o.compact_slots) o.compact_slots = d->compactSmall ? 8 * nCu : d->compactLargeSlots;     // (8: four wavefronts per SIMD by registers, two per workgroup)
+    if (!o.wide_slots) o.wide_slots = nCu;
+    if (!o.big_slots) o.big_slots = nCu;
+    if (!o.huge_slots) o.huge_slots = nCu / 4 ? nCu / 4 : 1;
+    if (!o.path_cap) o.path_cap = 32768;
+    if (!o.path_cap_max) o.path_cap_max = 1u << 20;
+    if (!o.arena) o.arena = 1u << 22;
+    if (o.path_cap_max < o.path_cap) o.path_cap_max = o.path_cap;
+    if (!o.max_views) o.max_views = 256;
+    if (!o.batch) o.batch = 65536;
+    if (!o.wide_threshold) o.wide_threshold = 2 * o.wide_slots;
+    if (!o.screen_min) o.screen_min = 2048;
+    if (o.path_cap & (o.path_cap - 1)) throw LcbError("lcb_device_opts.path_cap must be a power of two");
+}
+
+// the read-only tables (file header)
+void createTables(lcb_device_impl* d)
+{
+    const lcb_graph* g = d->g;
+    const LcbSegPlan& plan = d->plan;
+    const uint64_t nOcc = g->nPos();
+    {
+        std::vector<uint2> lh(g->nChr());
+        for (size_t c = 0; c < lh.size(); c++) lh[c] = uint2{plan.chrLo[c], plan.chrHi[c]};
+        d->T.chrLoHi = d->upload(lh.data(), lh.size());
+        d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
+    }
+    d->T.posId = d->uploadSeg(g->posId.data(), plan);
+    d->T.posPos = d->uploadSeg(g->posPos.data(), plan);
+    { const std::vector<uint32_t> win = lcb_window_table(*g, (uint32_t)d->p.max_branch); d->T.posWin = d->uploadSeg(win.data(), plan); }   // look-ahead windows (lcb_segments.h)
+    d->T.posCh = d->uploadSeg(g->posCh.data(), plan);
+    d->T.posRevCh = d->uploadSeg(g->posRevCh.data(), plan);
+    if (d->seg) { d->T.occStart64 = d->upload(g->occStart.data(), g->occStart.size()); d->T.occStart32 = nullptr; }
+    else {      // one segment: fewer than 2^32 occurrences
+        std::vector<uint32_t> os(g->occStart.begin(), g->occStart.end());
+        d->T.occStart32 = d->upload(os.data(), os.size()); d->T.occStart64 = nullptr;
+    }
+    std::vector<uint4> rec((size_t)nOcc);
+    #pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < (int64_t)nOcc; j++) {
+        const uint64_t q = g->occG[j];
+        const uint32_t cw = plan.chrWord[g->occChr[j]];
+        rec[j] = uint4{(uint32_t)(q - plan.segStart[cw >> LCB_SEG_SHIFT]), cw, g->posPos[q], (uint32_t)g->posId[q]};
+    }
+    d->T.occRec = d->upload(rec.data(), rec.size());
+}
+
+// the live bitmap with the pools of private pages behind it (the lanes' first, then the growing one of the synchronous launches), the
+// page tables of the synchronous launches' views, and the scalars of the tables and kernel parameters
+void createUsed(lcb_device_impl* d, uint32_t nLanes)
+{
+    const uint64_t P = d->plan.devPositions;     // length of the device tables (the occurrences + the test gaps)
+    const size_t pageWords = (size_t)1 << LCB_PAGE_SHIFT;
+    d->usedWords = ((size_t)(P / 32 + 2) + pageWords - 1) & ~(pageWords - 1);
+    d->nPages = (uint32_t)(d->usedWords >> LCB_PAGE_SHIFT);
+    // predicted `used` views for the engine's dry-run launches: a page table per view, private pages from a pool that grows on demand
+    d->maxViews = (int)d->o.max_views;
+    d->lanePoolPages = nLanes ? 32768u : 0u;
+    d->views.poolBasePage = nLanes * d->lanePoolPages;
+    d->views.poolPages = 4096;
+    // (+ 1 guard page: a vote walk that leaves its voter's page reads a few words past the private copy before it repairs the lane)
+    d->dUsed = d->devAlloc<uint32_t>((d->usedWords + ((size_t)d->views.poolBasePage + d->views.poolPages + 1) * pageWords) * 4);
+    HIP_CHECK(hipMemset(d->dUsed, 0, d->usedWords * 4));
+    d->views.tab = d->devAlloc<uint32_t>((size_t)(d->maxViews + 1) * d->nPages * 4);
+    HIP_CHECK(hipMemset(d->views.tab, 0, (size_t)(d->maxViews + 1) * d->nPages * 4));
+    d->T.used = d->dUsed; d->T.viewTab = d->views.tab; d->T.nPages = d->nPages;
+    d->T.nChr = d->g->nChr(); d->T.nVertex = d->g->nVertex; d->T.nPos = P; d->T.nSeg = d->plan.nSeg();
+    if (d->usedWords + (((uint64_t)d->views.poolBasePage + d->views.poolPages + 1) << LCB_PAGE_SHIFT) >= (1ull << 32)) throw LcbError("the `used` bitmap and its view pages need more than 2^32 words");
+    const lcb_params& p = d->p;
+    d->KP.k = p.k; d->KP.minBlock = p.min_block; d->KP.maxBranch = p.max_branch; d->KP.maxFlank = p.max_flank;
+    d->KP.depth = p.looking_depth;
+}
+
+// the control words and the workspace slots of the four variants
+void createWorkSets(lcb_device_impl* d)
+{
+    const lcb_device_opts& o = d->o;
+    d->dCursor = d->devAlloc<uint32_t>(32);
+    HIP_CHECK(hipMemset(d->dCursor, 0, 32));
+    // compact and wide: per-path state in LDS; bodies, result snapshot, checkpoint (and the compact path set) in a global slot
+    WorkSet& c = d->ws[0];
+    c.mode = 0; c.nSlots = o.compact_slots;
+    c.pathCap = o.path_cap; c.bodyCap = c.pathCap / 2; c.bestCap = LcbCfg<0>::IC;
+    d->allocWork(c);
+    WorkSet& w = d->ws[1];
+    w.mode = 1; w.nSlots = o.wide_slots;
+    w.pathCap = o.wide_path_cap ? o.wide_path_cap : LcbCfg<1>::PC;      // the set itself lives in LDS (PC slots); the slot keeps its insertion list
+    if (w.pathCap > LcbCfg<1>::PC || (w.pathCap & (w.pathCap - 1))) throw LcbError("lcb_device_opts.wide_path_cap must be a power of two, at most 8192");
+    w.bodyCap = w.pathCap / 2; w.bestCap = LcbCfg<1>::IC;
+    d->allocWork(w);
+    // big: instance fields in the slot; huge: everything in the slot, grown on demand
+    WorkSet& b = d->ws[2];
+    b.mode = 2; b.nSlots = o.big_slots;
+    b.pathCap = 262144; b.bodyCap = 131072; b.instCap = LcbCfg<2>::IC; b.voteCap = 0; b.bestCap = LcbCfg<2>::IC;
+    d->allocWork(b);
+    WorkSet& hg = d->ws[3];
+    hg.mode = 3; hg.nSlots = o.huge_slots;
+    hg.pathCap = 262144; hg.bodyCap = 131072; hg.instCap = 8192; hg.voteCap = 65536; hg.bestCap = 8192;
+    d->allocWork(hg);
+}
+
+// the two sets of pinned host buffers (their events exist since the queue was made)
+void createHostBufs(lcb_device_impl* d)
+{
+    d->batchCap = d->o.batch;
+    d->dLive = d->devAlloc<uint32_t>((size_t)d->batchCap * sizeof(uint32_t));
+    HostBufs& A = d->bufs;
+    A.live = d->pinnedAlloc<uint32_t>(((size_t)d->batchCap + 1) * sizeof(uint32_t));
+    A.seeds = d->pinnedAlloc<LcbKSeed>((size_t)d->batchCap * sizeof(LcbKSeed));
+    A.out = d->pinnedAlloc<LcbSeedOut>((size_t)d->batchCap * sizeof(LcbSeedOut));
+    d->hCtr = d->pinnedAlloc<LcbSeedCtr>((size_t)d->batchCap * sizeof(LcbSeedCtr));
+    d->allocArena(A, d->o.arena);
+    HostBufs& B = d->bufsEarly;
+    B.seeds = d->pinnedAlloc<LcbKSeed>((size_t)d->batchCap * sizeof(LcbKSeed));
+    B.out = d->pinnedAlloc<LcbSeedOut>((size_t)d->batchCap * sizeof(LcbSeedOut));
+    B.live = d->pinnedAlloc<uint32_t>(((size_t)d->batchCap + 1) * sizeof(uint32_t));
+    d->allocArena(B, d->o.arena);
+}
+
+// launch trace, instrumented flavour, bounded wait, flight recorder: all by the environment
+void createDiagnostics(lcb_device_impl* d)
+{
+    const char* tf = getenv("LCB_TRACE_LAUNCHES");
+    if (tf && *tf) d->traceFile = fopen(tf, "w");
+    d->seedTrace = envU32("LCB_TRACE_SEEDS", 0) != 0;
+    d->forceProf = envU32("LCB_FORCE_PROF", 0) != 0;
+    const char* wd = getenv("LCB_WATCHDOG_S");
+    d->watchdogS = wd && *wd ? atof(wd) : 0;
+    if (envU32("LCB_DEBUG", 0)) {
+        d->dbgSlots = std::max(std::max(d->ws[0].nSlots, d->ws[3].nSlots), std::max(d->ws[1].nSlots, d->ws[2].nSlots));
+        d->hDbg = d->pinnedAlloc<uint32_t>((size_t)d->dbgSlots * 16 * sizeof(uint32_t));
+    }
+}
+
+// side lanes: asynchronous job batches beside the synchronous launches (engine.cpp)
+void createLanes(lcb_device_impl* d, uint32_t nLanes, uint32_t nCu, int prioLow)
+{
+    lcb_device_opts& o = d->o;
+    d->ctlStream = d->newStream(nullptr);
+    d->lanes.resize(nLanes);
+    for (uint32_t l = 0; l < nLanes; l++) {
+        SideLane& L = d->lanes[l];
+        L.sw = d->newStream(&prioLow);
+        L.sb = d->newStream(&prioLow);
+        for (hipEvent_t* e : {&L.w0, &L.w1, &L.b0, &L.b1}) *e = d->newEvent();
+        L.cap = 2048; L.arenaCap = 1ull << 20;
+        // the host polls these while the kernels run: fine-grained (coherent) pinned memory
+        L.hSeeds = d->pinnedAlloc<LcbKSeed>((size_t)L.cap * sizeof(LcbKSeed), hipHostMallocCoherent);
+        L.hOut = d->pinnedAlloc<LcbSeedOut>((size_t)L.cap * sizeof(LcbSeedOut), hipHostMallocCoherent);
+        L.hArena = d->pinnedAlloc<uint4>((size_t)L.arenaCap * sizeof(uint4), hipHostMallocCoherent);
+        L.hFp = d->pinnedAlloc<LcbFpOut>((size_t)L.arenaCap * sizeof(LcbFpOut), hipHostMallocCoherent);
+        L.hList = d->pinnedAlloc<uint32_t>((size_t)2 * L.cap * sizeof(uint32_t), hipHostMallocCoherent);
+        L.hCtl = d->pinnedAlloc<uint32_t>(64, hipHostMallocCoherent);
+        L.dCtl = d->devAlloc<uint32_t>(64);
+        HIP_CHECK(hipMemset(L.dCtl, 0, 64));
+        L.views.tab = d->devAlloc<uint32_t>((size_t)(d->maxViews + 1) * d->nPages * 4);
+        HIP_CHECK(hipMemset(L.views.tab, 0, (size_t)(d->maxViews + 1) * d->nPages * 4));
+        L.views.poolBasePage = l * d->lanePoolPages; L.views.poolPages = d->lanePoolPages;
+        L.wide = d->ws[1]; L.wide.base = nullptr; L.wide.nSlots = std::max(1u, std::min(o.wide_slots, nCu / 2));
+        d->allocWork(L.wide);
+        L.big = d->ws[2]; L.big.base = nullptr; L.big.nSlots = std::max(1u, std::min(o.big_slots, (nCu * 3) / 8));
+        d->allocWork(L.big);
+        // A batch runs at most one wave of big-variant jobs (seeds known to need that variant: one workgroup per CU for tens of milliseconds,
+        // 2 GB of workspace writes per launch): beyond it heavy speculation is in the way of the commit's own launches more often than
+        // it is used. Config 3 -8 % per pass, the k = 25 shapes (few such jobs) unchanged; a third of that wave gains nothing
+        // (profiles/r05/ab_eighth_*.txt). The jobs over the cap get no result here: the commit computes them when it needs them.
+        if (!o.side_big_cap) o.side_big_cap = L.big.nSlots;
+    }
+}
+
+}  // namespace
 
 lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts)
 {
@@ -463,174 +695,27 @@ lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int 
     try {
         d->ordinal = ordinal; d->g = g; d->p = *p;
         if (opts) d->o = *opts;
-        lcb_device_opts& o = d->o;
         d->use();
         hipDeviceProp_t prop;
         HIP_CHECK(hipGetDeviceProperties(&prop, ordinal));
         const uint32_t nCu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
-        // positions: (segment, g) pairs (lcb_segments.h); seg_cap / seg_gap are test hooks (small segments on small inputs, flat indices
-        // beyond 2^32 through unused table space between the segments)
-        d->plan = lcb_plan_segments(*g, o.seg_cap, o.seg_gap);
-        d->seg = d->plan.nSeg() > 1 || o.seg_cap != 0;
-        // defaults: compact 5 workgroups per CU (LDS-bound; 4 with the segment tables of the SEG kernels), wide 1 per CU, big 1 per CU
-        // the compact variant's pools: small ones where a vertex has few occurrences (paths of few instances: k = 25 inputs of 8-16 genomes, 6-12
-        // occurrences per vertex; the 62-strain shape has 26 at 1/40 of its size and more at full size, and its paths outgrow 128 instances)
-        if (o.compact_pools > 2) throw LcbError("lcb_device_opts.compact_pools: 0 (by the input), 1 (256 instances / 1 024 vote slots) or 2 (128 / 512)");
-        d->compactAuto = o.compact_pools == 0;
-        // (the occurrence-weighted mean of the occurrences per vertex: "the typical occurrence belongs to a vertex with that many" - 6-14 for the k = 25 shapes of 8 / 16
-        // genomes, 35+ for the 62-strain shape, 25 for the 10-strain one, whose many strain-private vertices would hide that in a plain mean)
-        long double occSq = 0;
-        for (size_t v = 0; v + 1 < g->occStart.size(); v++) { const long double nv = (long double)(g->occStart[v + 1] - g->occStart[v]); occSq += nv * nv; }
-        d->compactSmall = o.compact_pools == 2 || (o.compact_pools == 0 && g->nPos() > 0 && occSq <= 20.0L * (long double)g->nPos());
-        d->compactLargeSlots = o.compact_slots ? o.compact_slots : (d->seg ? 4 : 5) * nCu;
-        if (!o.compact_slots) o.compact_slots = d->compactSmall ? 8 * nCu : d->compactLargeSlots;     // (8: four wavefronts per SIMD by registers, two per workgroup)
-        if (!o.wide_slots) o.wide_slots = nCu;
-        if (!o.big_slots) o.big_slots = nCu;
-        if (!o.huge_slots) o.huge_slots = nCu / 4 ? nCu / 4 : 1;
-        if (!o.path_cap) o.path_cap = 32768;
-        if (!o.path_cap_max) o.path_cap_max = 1u << 20;
-        if (!o.arena) o.arena = 1u << 22;
-        if (o.path_cap_max < o.path_cap) o.path_cap_max = o.path_cap;
-        if (!o.max_views) o.max_views = 256;
-        if (!o.batch) o.batch = 65536;
-        if (!o.wide_threshold) o.wide_threshold = 2 * o.wide_slots;
-        if (!o.screen_min) o.screen_min = 2048;
-        if (o.path_cap & (o.path_cap - 1)) throw LcbError("lcb_device_opts.path_cap must be a power of two");
+        createOptions(d, nCu);
         // needed results ahead of speculation: the stream of the synchronous launches gets the highest HIP stream priority, the side
         // lanes' streams the lowest (numerically lower = higher priority; -4 % per pass together with the early critical launch,
         // profiles/r04/ab_first.txt)
         int prioLow = 0, prioHigh = 0;
         HIP_CHECK(hipDeviceGetStreamPriorityRange(&prioLow, &prioHigh));
-        HIP_CHECK(hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, prioHigh));
-        HIP_CHECK(hipEventCreate(&d->ev0));
-        HIP_CHECK(hipEventCreate(&d->ev1));
-        HIP_CHECK(hipEventCreate(&d->ev2));
-        HIP_CHECK(hipEventCreate(&d->ev3));
-        const LcbSegPlan& plan = d->plan;
-        const uint64_t nOcc = g->nPos(), P = plan.devPositions;      // P: length of the device tables (the occurrences + the test gaps)
-        {
-            std::vector<uint2> lh(g->nChr());
-            for (size_t c = 0; c < lh.size(); c++) lh[c] = uint2{plan.chrLo[c], plan.chrHi[c]};
-            d->T.chrLoHi = d->upload(lh.data(), lh.size());
-            d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
-        }
-        d->T.posId = d->uploadSeg(g->posId.data(), plan);
-        d->T.posPos = d->uploadSeg(g->posPos.data(), plan);
-        { const std::vector<uint32_t> win = lcb_window_table(*g, (uint32_t)p->max_branch); d->T.posWin = d->uploadSeg(win.data(), plan); }   // look-ahead windows (lcb_segments.h)
-        d->T.posCh = d->uploadSeg(g->posCh.data(), plan);
-        d->T.posRevCh = d->uploadSeg(g->posRevCh.data(), plan);
-        if (d->seg) { d->T.occStart64 = d->upload(g->occStart.data(), g->occStart.size()); d->T.occStart32 = nullptr; }
-        else {      // one segment: fewer than 2^32 occurrences
-            std::vector<uint32_t> os(g->occStart.begin(), g->occStart.end());
-            d->T.occStart32 = d->upload(os.data(), os.size()); d->T.occStart64 = nullptr;
-        }
-        {
-            std::vector<uint4> rec((size_t)nOcc);
-            #pragma omp parallel for schedule(static)
-            for (int64_t j = 0; j < (int64_t)nOcc; j++) {
-                const uint64_t q = g->occG[j];
-                const uint32_t cw = plan.chrWord[g->occChr[j]];
-                rec[j] = uint4{(uint32_t)(q - plan.segStart[cw >> LCB_SEG_SHIFT]), cw, g->posPos[q], (uint32_t)g->posId[q]};
-            }
-            d->T.occRec = d->upload(rec.data(), rec.size());
-        }
-        const size_t pageWords = (size_t)1 << LCB_PAGE_SHIFT;
-        d->usedWords = ((size_t)(P / 32 + 2) + pageWords - 1) & ~(pageWords - 1);
-        d->nPages = (uint32_t)(d->usedWords >> LCB_PAGE_SHIFT);
-        // predicted `used` views for the engine's dry-run launches: a page table per view, private pages from a pool that grows on demand
-        d->maxViews = (int)o.max_views;
-        const uint32_t nLanes = o.side_lanes == 0xFFFFFFFFu ? 0u : (o.side_lanes ? o.side_lanes : 4u);
-        d->lanePoolPages = nLanes ? 32768u : 0u;
-        d->views.poolBasePage = nLanes * d->lanePoolPages;
-        d->views.poolPages = 4096;
-        // (+ 1 guard page: a vote walk that leaves its voter's page reads a few words past the private copy before it repairs the lane)
-        HIP_CHECK(hipMalloc((void**)&d->dUsed, (d->usedWords + ((size_t)d->views.poolBasePage + d->views.poolPages + 1) * pageWords) * 4));
-        HIP_CHECK(hipMemset(d->dUsed, 0, d->usedWords * 4));
-        HIP_CHECK(hipMalloc((void**)&d->views.tab, (size_t)(d->maxViews + 1) * d->nPages * 4));
-        HIP_CHECK(hipMemset(d->views.tab, 0, (size_t)(d->maxViews + 1) * d->nPages * 4));
-        d->T.used = d->dUsed; d->T.viewTab = d->views.tab; d->T.nPages = d->nPages;
-        d->T.nChr = g->nChr(); d->T.nVertex = g->nVertex; d->T.nPos = P; d->T.nSeg = plan.nSeg();
-        if (d->usedWords + (((uint64_t)d->views.poolBasePage + d->views.poolPages + 1) << LCB_PAGE_SHIFT) >= (1ull << 32)) throw LcbError("the `used` bitmap and its view pages need more than 2^32 words");
-        d->KP.k = p->k; d->KP.minBlock = p->min_block; d->KP.maxBranch = p->max_branch; d->KP.maxFlank = p->max_flank;
-        d->KP.depth = p->looking_depth;
-        HIP_CHECK(hipMalloc((void**)&d->dCursor, 32));
-        HIP_CHECK(hipMemset(d->dCursor, 0, 32));
-        // compact and wide: per-path state in LDS; bodies, result snapshot, checkpoint (and the compact path set) in a global slot
-        WorkSet& c = d->ws[0];
-        c.mode = 0; c.nSlots = o.compact_slots;
-        c.pathCap = o.path_cap; c.bodyCap = c.pathCap / 2; c.bestCap = LcbCfg<0>::IC;
-        d->allocWork(c);
-        WorkSet& w = d->ws[1];
-        w.mode = 1; w.nSlots = o.wide_slots;
-        w.pathCap = o.wide_path_cap ? o.wide_path_cap : LcbCfg<1>::PC;      // the set itself lives in LDS (PC slots); the slot keeps its insertion list
-        if (w.pathCap > LcbCfg<1>::PC || (w.pathCap & (w.pathCap - 1))) throw LcbError("lcb_device_opts.wide_path_cap must be a power of two, at most 8192");
-        w.bodyCap = w.pathCap / 2; w.bestCap = LcbCfg<1>::IC;
-        d->allocWork(w);
-        // big: instance fields in the slot; huge: everything in the slot, grown on demand
-        WorkSet& b = d->ws[2];
-        b.mode = 2; b.nSlots = o.big_slots;
-        b.pathCap = 262144; b.bodyCap = 131072; b.instCap = LcbCfg<2>::IC; b.voteCap = 0; b.bestCap = LcbCfg<2>::IC;
-        d->allocWork(b);
-        WorkSet& hg = d->ws[3];
-        hg.mode = 3; hg.nSlots = o.huge_slots;
-        hg.pathCap = 262144; hg.bodyCap = 131072; hg.instCap = 8192; hg.voteCap = 65536; hg.bestCap = 8192;
-        d->allocWork(hg);
-        d->batchCap = o.batch;
-        HIP_CHECK(hipMalloc((void**)&d->dLive, (size_t)d->batchCap * sizeof(uint32_t)));
-        HIP_CHECK(hipHostMalloc((void**)&d->hLive, ((size_t)d->batchCap + 1) * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&d->hSeeds, (size_t)d->batchCap * sizeof(LcbKSeed), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&d->hOut, (size_t)d->batchCap * sizeof(LcbSeedOut), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&d->hCtr, (size_t)d->batchCap * sizeof(LcbSeedCtr), hipHostMallocDefault));
-        d->allocArena(o.arena);
-        d->swapBufs();
-        HIP_CHECK(hipHostMalloc((void**)&d->hSeeds, (size_t)d->batchCap * sizeof(LcbKSeed), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&d->hOut, (size_t)d->batchCap * sizeof(LcbSeedOut), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&d->hLive, ((size_t)d->batchCap + 1) * sizeof(uint32_t), hipHostMallocDefault));
-        d->allocArena(o.arena);
-        d->swapBufs();
-        const char* tf = getenv("LCB_TRACE_LAUNCHES");
-        if (tf && *tf) d->traceFile = fopen(tf, "w");
-        d->seedTrace = envU32("LCB_TRACE_SEEDS", 0) != 0;
-        d->forceProf = envU32("LCB_FORCE_PROF", 0) != 0;
-        const char* wd = getenv("LCB_WATCHDOG_S");
-        d->watchdogS = wd && *wd ? atof(wd) : 0;
-        if (envU32("LCB_DEBUG", 0)) {
-            d->dbgSlots = std::max(std::max(c.nSlots, hg.nSlots), std::max(w.nSlots, b.nSlots));
-            HIP_CHECK(hipHostMalloc((void**)&d->hDbg, (size_t)d->dbgSlots * 16 * sizeof(uint32_t), hipHostMallocDefault));
-        }
+        d->stream = d->newStream(&prioHigh);
+        for (hipEvent_t* e : {&d->bufs.e0, &d->bufs.e1, &d->bufsEarly.e0, &d->bufsEarly.e1}) *e = d->newEvent();
+        const uint32_t nLanes = d->o.side_lanes == 0xFFFFFFFFu ? 0u : (d->o.side_lanes ? d->o.side_lanes : 4u);
+        createTables(d);
+        createUsed(d, nLanes);
+        createWorkSets(d);
+        createHostBufs(d);
+        createDiagnostics(d);
         d->rangeCap = 65536;
-        HIP_CHECK(hipHostMalloc((void**)&d->hRanges, (size_t)d->rangeCap * sizeof(LcbMarkRange), hipHostMallocDefault));
-        // side lanes: asynchronous job batches beside the synchronous launches (engine.cpp)
-        HIP_CHECK(hipStreamCreateWithFlags(&d->ctlStream, hipStreamNonBlocking));
-        d->lanes.resize(nLanes);
-        for (uint32_t l = 0; l < nLanes; l++) {
-            SideLane& L = d->lanes[l];
-            HIP_CHECK(hipStreamCreateWithPriority(&L.sw, hipStreamNonBlocking, prioLow));
-            HIP_CHECK(hipStreamCreateWithPriority(&L.sb, hipStreamNonBlocking, prioLow));
-            for (hipEvent_t* e : {&L.w0, &L.w1, &L.b0, &L.b1}) HIP_CHECK(hipEventCreate(e));
-            L.cap = 2048; L.arenaCap = 1ull << 20;
-            // the host polls these while the kernels run: fine-grained (coherent) pinned memory
-            HIP_CHECK(hipHostMalloc((void**)&L.hSeeds, (size_t)L.cap * sizeof(LcbKSeed), hipHostMallocCoherent));
-            HIP_CHECK(hipHostMalloc((void**)&L.hOut, (size_t)L.cap * sizeof(LcbSeedOut), hipHostMallocCoherent));
-            HIP_CHECK(hipHostMalloc((void**)&L.hArena, (size_t)L.arenaCap * sizeof(uint4), hipHostMallocCoherent));
-            HIP_CHECK(hipHostMalloc((void**)&L.hFp, (size_t)L.arenaCap * sizeof(LcbFpOut), hipHostMallocCoherent));
-            HIP_CHECK(hipHostMalloc((void**)&L.hList, (size_t)2 * L.cap * sizeof(uint32_t), hipHostMallocCoherent));
-            HIP_CHECK(hipHostMalloc((void**)&L.hCtl, 64, hipHostMallocCoherent));
-            HIP_CHECK(hipMalloc((void**)&L.dCtl, 64));
-            HIP_CHECK(hipMemset(L.dCtl, 0, 64));
-            HIP_CHECK(hipMalloc((void**)&L.views.tab, (size_t)(d->maxViews + 1) * d->nPages * 4));
-            HIP_CHECK(hipMemset(L.views.tab, 0, (size_t)(d->maxViews + 1) * d->nPages * 4));
-            L.views.poolBasePage = l * d->lanePoolPages; L.views.poolPages = d->lanePoolPages;
-            L.wide = d->ws[1]; L.wide.base = nullptr; L.wide.nSlots = std::max(1u, std::min(o.wide_slots, nCu / 2));
-            d->allocWork(L.wide);
-            L.big = d->ws[2]; L.big.base = nullptr; L.big.nSlots = std::max(1u, std::min(o.big_slots, (nCu * 3) / 8));
-            d->allocWork(L.big);
-            // A batch runs at most one wave of big-variant jobs (seeds known to need that variant: one workgroup per CU for tens of milliseconds,
-            // 2 GB of workspace writes per launch): beyond it heavy speculation is in the way of the commit's own launches more often than
-            // it is used. Config 3 -8 % per pass, the k = 25 shapes (few such jobs) unchanged; a third of that wave gains nothing
-            // (profiles/r05/ab_eighth_*.txt). The jobs over the cap get no result here: the commit computes them when it needs them.
-            if (!o.side_big_cap) o.side_big_cap = L.big.nSlots;
-        }
+        d->hRanges = d->pinnedAlloc<LcbMarkRange>((size_t)d->rangeCap * sizeof(LcbMarkRange));
+        createLanes(d, nLanes, nCu, prioLow);
     } catch (...) {
         lcb_device_destroy_impl(handle);
         throw;
@@ -657,7 +742,7 @@ void lcb_device_destroy_impl(lcb_device* h)
             fprintf(stderr, "   results remembered as too long for the wide variant's path set: %lld\n", (long long)d->longPathHints);
             fprintf(stderr, "   compact pools: %s (%u workgroups), %lld live seeds ended there, %lld outgrew its pools%s\n", d->compactSmall ? "128 instances / 512 vote slots" : "256 instances / 1 024 vote slots", d->ws[0].nSlots,
                     (long long)d->compactDone, (long long)d->compactPoolOvf, d->compactFellBack ? " - the small pools were given up" : "");
-            fprintf(stderr, "   result arena: %llu instances (enlarged %d times)\n", d->arenaCap, d->arenaGrown);
+            fprintf(stderr, "   result arena: %llu instances (enlarged %d times)\n", d->bufs.arenaCap, d->arenaGrown);
             fprintf(stderr, "   seeds that joined a call's big launch instead of a wide launch in front of it: %lld\n", (long long)d->joinedBig);
             for (int m = 0; m < 4; m++)
                 fprintf(stderr, "   overflows out of %-7s: instances %lld vote table %lld path %lld snapshot %lld\n", modeName(m), (long long)d->overflow[m][LCB_ST_INST_OVF],
@@ -665,38 +750,8 @@ void lcb_device_destroy_impl(lcb_device* h)
         }
         (void)hipSetDevice(d->ordinal);
         if (d->stream) (void)hipStreamSynchronize(d->stream);
-        for (void* p : d->owned) (void)hipFree(p);
-        if (d->dUsed) (void)hipFree(d->dUsed);
-        for (SideLane& L : d->lanes) {
-            for (hipStream_t q : {L.sw, L.sb}) if (q) (void)hipStreamDestroy(q);
-            for (hipEvent_t e : {L.w0, L.w1, L.b0, L.b1}) if (e) (void)hipEventDestroy(e);
-            for (void* q : {(void*)L.hSeeds, (void*)L.hOut, (void*)L.hArena, (void*)L.hFp, (void*)L.hList, (void*)L.hCtl}) if (q) (void)hipHostFree(q);
-            for (void* q : {(void*)L.dCtl, (void*)L.views.tab, (void*)L.views.dEntries, (void*)L.views.dVersions, (void*)L.views.dPieces, (void*)L.wide.base, (void*)L.big.base}) if (q) (void)hipFree(q);
-        }
-        if (d->ctlStream) (void)hipStreamDestroy(d->ctlStream);
-        if (d->views.tab) (void)hipFree(d->views.tab);
-        if (d->views.dEntries) (void)hipFree(d->views.dEntries);
-        if (d->views.dPieces) (void)hipFree(d->views.dPieces);
-        if (d->views.dVersions) (void)hipFree(d->views.dVersions);
-        if (d->dCursor) (void)hipFree(d->dCursor);
-        if (d->dLive) (void)hipFree(d->dLive);
-        if (d->hLive) (void)hipHostFree(d->hLive);
-        for (auto& w : d->ws) if (w.base) (void)hipFree(w.base);
-        for (void* q : {(void*)d->hSeedsB, (void*)d->hOutB, (void*)d->hArenaB, (void*)d->hFpB, (void*)d->hLiveB}) if (q) (void)hipHostFree(q);
-        if (d->ev2) (void)hipEventDestroy(d->ev2);
-        if (d->ev3) (void)hipEventDestroy(d->ev3);
-        if (d->hSeeds) (void)hipHostFree(d->hSeeds);
-        if (d->hOut) (void)hipHostFree(d->hOut);
-        if (d->hCtr) (void)hipHostFree(d->hCtr);
-        if (d->hArena) (void)hipHostFree(d->hArena);
-        if (d->hFp) (void)hipHostFree(d->hFp);
-        if (d->hRanges) (void)hipHostFree(d->hRanges);
-        if (d->hDbg) (void)hipHostFree(d->hDbg);
+        d->own.releaseAll();              // whatever was made, a half-made device's included
         if (d->traceFile) fclose(d->traceFile);
-        if (d->evBase) (void)hipEventDestroy(d->evBase);
-        if (d->ev0) (void)hipEventDestroy(d->ev0);
-        if (d->ev1) (void)hipEventDestroy(d->ev1);
-        if (d->stream) (void)hipStreamDestroy(d->stream);
         delete d;
     }
     delete h;
@@ -801,15 +856,21 @@ static bool lcb_build_views_into(lcb_device_impl* d, ViewSpace& V, hipStream_t s
         uint32_t np = V.poolPages;
         while (np < versions.size()) np *= 2;
         if (d->usedWords + (((uint64_t)V.poolBasePage + np) << LCB_PAGE_SHIFT) >= (1ull << 32)) throw LcbError("predicted views need more private pages than a 32-bit word offset reaches");
-        uint32_t* nu = nullptr;
-        HIP_CHECK(hipMalloc((void**)&nu, (d->usedWords + (((size_t)V.poolBasePage + np + 1) << LCB_PAGE_SHIFT)) * 4));
+        uint32_t* nu = d->devAlloc<uint32_t>((d->usedWords + (((size_t)V.poolBasePage + np + 1) << LCB_PAGE_SHIFT)) * 4);
         HIP_CHECK(hipMemcpy(nu, d->dUsed, d->usedWords * 4, hipMemcpyDeviceToDevice));
-        HIP_CHECK(hipFree(d->dUsed));
+        d->drop(d->dUsed);
         d->dUsed = nu; V.poolPages = np; d->T.used = nu;
     }
-    if (entries.size() > V.entryCap) { if (V.dEntries) HIP_CHECK(hipFree(V.dEntries)); V.entryCap = entries.size() * 2; HIP_CHECK(hipMalloc((void**)&V.dEntries, V.entryCap * sizeof(LcbViewPage))); }
-    if (versions.size() > V.versionCap) { if (V.dVersions) HIP_CHECK(hipFree(V.dVersions)); V.versionCap = versions.size() * 2; HIP_CHECK(hipMalloc((void**)&V.dVersions, V.versionCap * sizeof(LcbViewVersion))); }
-    if (pieces.size() > V.pieceCap) { if (V.dPieces) HIP_CHECK(hipFree(V.dPieces)); V.pieceCap = pieces.size() * 2; HIP_CHECK(hipMalloc((void**)&V.dPieces, V.pieceCap * sizeof(LcbViewPiece))); }
+    // staging of the lists on the device, made again at twice the need when they are too small
+    auto fit = [d](auto*& buf, size_t& cap, size_t need) {
+        if (need <= cap) return;
+        d->drop(buf);
+        cap = need * 2;
+        buf = d->devAlloc<std::remove_reference_t<decltype(*buf)>>(cap * sizeof(*buf));
+    };
+    fit(V.dEntries, V.entryCap, entries.size());
+    fit(V.dVersions, V.versionCap, versions.size());
+    fit(V.dPieces, V.pieceCap, pieces.size());
     HIP_CHECK(hipMemcpyAsync(V.dEntries, entries.data(), entries.size() * sizeof(LcbViewPage), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(V.dVersions, versions.data(), versions.size() * sizeof(LcbViewVersion), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(V.dPieces, pieces.data(), pieces.size() * sizeof(LcbViewPiece), hipMemcpyHostToDevice, stream));
@@ -843,12 +904,12 @@ double lcb_device_hbm_triad_impl(lcb_device* h, uint64_t bytes, int reps)
     HIP_CHECK(hipMemsetAsync(c, 0, n * sizeof(float4), d->stream));
     float ms = 0;
     for (int r = 0; r <= reps; r++) {
-        if (r == 1) HIP_CHECK(hipEventRecord(d->ev0, d->stream));
+        if (r == 1) HIP_CHECK(hipEventRecord(d->bufs.e0, d->stream));
         hipLaunchKernelGGL(lcb_triad_kernel, dim3(256 * 32), dim3(256), 0, d->stream, a, b, c, 3.0f, n);
     }
-    HIP_CHECK(hipEventRecord(d->ev1, d->stream));
+    HIP_CHECK(hipEventRecord(d->bufs.e1, d->stream));
     HIP_CHECK(hipStreamSynchronize(d->stream));
-    HIP_CHECK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+    HIP_CHECK(hipEventElapsedTime(&ms, d->bufs.e0, d->bufs.e1));
     (void)hipFree(a); (void)hipFree(b); (void)hipFree(c);
     return ms > 0 ? 3.0 * (double)(n * sizeof(float4)) * reps / (ms * 1e-3) / 1e9 : 0.0;
 }
@@ -916,14 +977,50 @@ struct ProcAcc {
     int64_t neededBig = 0;                              // seeds that finished in the big / huge variant and could not have run in a smaller one
 };
 
+// A seed's key in modeHint and its bit in the prefilter in front of it.
 uint64_t hintKey(const lcb_seed& sd) { return ((uint64_t)(uint32_t)sd.vid << 8) | (uint64_t)(uint8_t)sd.ch; }
+uint32_t hintBit(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 48); }
 
 void setHint(lcb_device_impl* d, const lcb_seed& sd, uint8_t mode)
 {
     const uint64_t key = hintKey(sd);
-    const uint32_t hb = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 48);
+    const uint32_t hb = hintBit(key);
     d->hintBits[hb >> 6] |= 1ull << (hb & 63);
     d->modeHint[key] = mode;
+}
+
+// The variant a seed is known to need, or dflt.
+uint8_t hintOf(const lcb_device_impl* d, const lcb_seed& sd, uint8_t dflt)
+{
+    const uint64_t key = hintKey(sd);
+    const uint32_t hb = hintBit(key);
+    if (d->modeHint.empty() || !((d->hintBits[hb >> 6] >> (hb & 63)) & 1ull)) return dflt;
+    const auto it = d->modeHint.find(key);
+    return it != d->modeHint.end() ? it->second : dflt;
+}
+
+LcbKSeed kernelSeed(const lcb_seed& sd, uint32_t view) { return LcbKSeed{sd.vid, sd.ch, view, 0}; }
+
+// lcb_counters and the first eight words of a seed's LcbSeedCtr (stats flavour) are the same counters in the same order.
+uint64_t lcb_counters::* const kCounters[8] = {&lcb_counters::n_walk, &lcb_counters::n_occ, &lcb_counters::n_compat_call, &lcb_counters::n_compat_step,
+                                               &lcb_counters::n_inst_out, &lcb_counters::n_vote, &lcb_counters::n_push, &lcb_counters::n_process};
+lcb_counters countersOf(const LcbSeedCtr& k)
+{
+    lcb_counters q{};
+    for (int j = 0; j < 8; j++) q.*kCounters[j] = k.c[j];
+    return q;
+}
+
+// Appends the instances (and, with fp, the footprint intervals) of the finished seed with header o to inst (fpOut).
+void appendResult(const LcbSegPlan& plan, const LcbSeedOut& o, const uint4* arena, const LcbFpOut* fp, std::vector<lcb_instance>& inst, std::vector<lcb_fp>& fpOut)
+{
+    const uint4* src = arena + o.arenaOff;
+    const size_t f0 = inst.size(), g0 = fpOut.size();
+    inst.resize(f0 + o.nInst);
+    for (uint32_t e = 0; e < o.nInst; e++) inst[f0 + e] = lcb_instance{src[e].x, src[e].y, src[e].z, src[e].w};
+    if (!fp) return;
+    fpOut.resize(g0 + o.nFp);
+    for (uint32_t e = 0; e < o.nFp; e++) fpOut[g0 + e] = lcb_fp{plan.toHost(fp[o.fpOff + e].lo), plan.toHost(fp[o.fpOff + e].hi)};
 }
 
 void accInit(lcb_device_impl* d, ProcAcc& A, const lcb_seed* seeds, int64_t n, const uint32_t* view, int64_t* bestScore, lcb_counters* ctr,
@@ -942,9 +1039,7 @@ void accInit(lcb_device_impl* d, ProcAcc& A, const lcb_seed* seeds, int64_t n, c
         A.start.assign((size_t)n, (uint8_t)base);
         int64_t nBig = 0;
         for (int64_t s = 0; s < n; s++) {
-            const uint64_t key = hintKey(seeds[s]);
-            const uint32_t hb = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 48);
-            if ((d->hintBits[hb >> 6] >> (hb & 63)) & 1ull) { auto it = d->modeHint.find(key); if (it != d->modeHint.end()) A.start[(size_t)s] = it->second; }
+            A.start[(size_t)s] = hintOf(d, seeds[s], (uint8_t)base);
             nBig += A.start[(size_t)s] >= 2;
         }
         // Variants run one after the other and a launch lasts as long as its longest seed. In the stretch of the seed order
@@ -961,24 +1056,44 @@ void accInit(lcb_device_impl* d, ProcAcc& A, const lcb_seed* seeds, int64_t n, c
     }
 }
 
-void fillSeeds(lcb_device_impl* d, const ProcAcc& A, const std::vector<int64_t>& list, size_t at, uint32_t m)
+void fillSeeds(HostBufs& B, const ProcAcc& A, const std::vector<int64_t>& list, size_t at, uint32_t m)
 {
     for (uint32_t i = 0; i < m; i++) {
         const int64_t s = list[at + i];
-        d->hSeeds[i].vid = A.seeds[s].vid; d->hSeeds[i].ch = A.seeds[s].ch; d->hSeeds[i].view = A.view ? A.view[s] : 0u; d->hSeeds[i].pad = 0;
+        B.seeds[i] = kernelSeed(A.seeds[s], A.view ? A.view[s] : 0u);
     }
 }
 
-// Takes the results of one finished launch out of the host buffers; seeds that overflowed go to the next variant's list.
+// The next variant of a seed that left variant `mode` with the overflow `status`; tried: the variants it overflowed in this call
+// (bit m, `mode` included), poolInst: the instances it held at the end, compactIC: the compact variant's instance pool,
+// pathCanGrow: the compact path set is below its maximum. GROW_COMPACT_PATH: the compact variant again, after its path set was enlarged.
+// The ladder is compact -> wide -> big -> huge by capacity of instances and vote table, but the
+// PATH capacity is the other way round between the first two: the wide variant keeps its path set in LDS (4096
+// vertices), the compact one in HBM (65 536). A long path with few instances (long blocks of few genomes, k = 25)
+// that started in the wide variant therefore goes back to the compact one - unless it already holds more
+// instances than half the compact pool (the repeat-rich seeds of config 3: thousands of instances AND > 4096
+// pushes; they would crawl through the compact variant only to overflow its pool) - the rest goes on to big.
+const int GROW_COMPACT_PATH = -1;
+int nextVariant(int mode, uint32_t status, uint8_t tried, uint32_t poolInst, uint32_t compactIC, bool pathCanGrow)
+{
+    const bool fewInst = poolInst * 2 <= compactIC;
+    if (mode == 1 && status == LCB_ST_PATH_OVF && !(tried & 1u) && fewInst) return 0;
+    if (mode == 0 && status == LCB_ST_PATH_OVF && pathCanGrow && fewInst) return GROW_COMPACT_PATH;     // a long path of few instances
+    if (mode == 0 && status == LCB_ST_PATH_OVF) return 2;
+    if (mode == 0 && (tried & 2u)) return 2;
+    return mode < 3 ? mode + 1 : 3;
+}
+
+// Takes the results of one finished launch out of its host buffers; seeds that overflowed go to the next variant's list.
 // Returns true if a seed overflowed the huge variant (its capacities must grow).
-bool gatherBatch(lcb_device_impl* d, ProcAcc& A, const std::vector<int64_t>& list, size_t at, uint32_t m, bool screen, int mode)
+bool gatherBatch(lcb_device_impl* d, const HostBufs& B, ProcAcc& A, const std::vector<int64_t>& list, size_t at, uint32_t m, bool screen, int mode)
 {
     bool hugeOverflow = false;
-    const uint32_t nLook = screen ? d->hLive[d->batchCap] : m;   // seeds the screening finalised (no instance, no footprint) keep their zeros
+    const uint32_t nLook = screen ? B.live[d->batchCap] : m;   // seeds the screening finalised (no instance, no footprint) keep their zeros
     if (screen) { d->screened += m; d->screenedDead += m - nLook; }
     for (uint32_t t = 0; t < nLook; t++) {
-        const uint32_t i = screen ? d->hLive[t] : t;
-        const LcbSeedOut& o = d->hOut[i];
+        const uint32_t i = screen ? B.live[t] : t;
+        const LcbSeedOut& o = B.out[i];
         const int64_t s = list[at + i];
         if (o.status == LCB_ST_OK) {
             if (mode == 0 && o.nFp) d->compactDone++;
@@ -987,37 +1102,20 @@ bool gatherBatch(lcb_device_impl* d, ProcAcc& A, const std::vector<int64_t>& lis
             // over elsewhere. It is remembered like an overflow: the next attempt begins in the compact variant (a lane: in the big one).
             if (mode == 0 && o.nInst && !d->o.start_mode) {
                 // (the first instance stands for all: the instances of a block span about the same number of junctions, and this loop runs for every result)
-                const uint4 r0 = d->hArena[o.arenaOff];
+                const uint4 r0 = B.arena[o.arenaOff];
                 const uint32_t span = r0.y > r0.z ? r0.y - r0.z : r0.z - r0.y;
                 if ((uint64_t)span * 8 >= (uint64_t)d->ws[1].pathCap * 3) { setHint(d, A.seeds[s], 0); d->longPathHints++; }
             }
             if (mode >= 2 && (!(A.allBig && A.start[(size_t)s] < 2) || o.poolInst > LcbCfg<1>::IC)) A.neededBig++;
             A.cnt[(size_t)s] = o.nInst;
             A.flatOff[(size_t)s] = A.flat.size();
-            if (o.nInst) {
-                const uint4* src = d->hArena + o.arenaOff;
-                const size_t f0 = A.flat.size();
-                A.flat.resize(f0 + o.nInst);
-                for (uint32_t e = 0; e < o.nInst; e++) A.flat[f0 + e] = lcb_instance{src[e].x, src[e].y, src[e].z, src[e].w};
-            }
+            if (A.wantFp) { A.fpAt[(size_t)s] = A.fpFlat.size(); A.fpCnt[(size_t)s] = o.nFp; }
+            appendResult(d->plan, o, B.arena, A.wantFp ? B.fp : nullptr, A.flat, A.fpFlat);
             if (A.bestScore) A.bestScore[s] = o.bestScore;
-            if (A.wantFp) {
-                A.fpAt[(size_t)s] = A.fpFlat.size(); A.fpCnt[(size_t)s] = o.nFp;
-                const LcbFpOut* src = d->hFp + o.fpOff;
-                const size_t f0 = A.fpFlat.size();
-                A.fpFlat.resize(f0 + o.nFp);
-                for (uint32_t e = 0; e < o.nFp; e++) A.fpFlat[f0 + e] = lcb_fp{d->plan.toHost(src[e].lo), d->plan.toHost(src[e].hi)};
-            }
-            if (A.perSeedCtr && d->stats) {
-                const LcbSeedCtr& k = d->hCtr[i];
-                lcb_counters& q = (*A.perSeedCtr)[(size_t)s];
-                q.n_walk = k.c[0]; q.n_occ = k.c[1]; q.n_compat_call = k.c[2]; q.n_compat_step = k.c[3];
-                q.n_inst_out = k.c[4]; q.n_vote = k.c[5]; q.n_push = k.c[6]; q.n_process = k.c[7];
-            }
-            if (A.ctr) {
-                const LcbSeedCtr& k = d->hCtr[i];
-                A.ctr->n_walk += k.c[0]; A.ctr->n_occ += k.c[1]; A.ctr->n_compat_call += k.c[2]; A.ctr->n_compat_step += k.c[3];
-                A.ctr->n_inst_out += k.c[4]; A.ctr->n_vote += k.c[5]; A.ctr->n_push += k.c[6]; A.ctr->n_process += k.c[7];
+            if ((A.perSeedCtr && d->stats) || A.ctr) {
+                const lcb_counters q = countersOf(d->hCtr[i]);
+                if (A.perSeedCtr && d->stats) (*A.perSeedCtr)[(size_t)s] = q;
+                if (A.ctr) for (int j = 0; j < 8; j++) A.ctr->*kCounters[j] += q.*kCounters[j];
             }
         } else if (o.status == LCB_ST_DIST_OVF) {
             throw LcbError("a path longer than 2^31 bp is not supported");
@@ -1030,23 +1128,14 @@ bool gatherBatch(lcb_device_impl* d, ProcAcc& A, const std::vector<int64_t>& lis
             if (o.status < 8) d->overflow[mode][o.status]++;
             if (mode == 0 && (o.status == LCB_ST_INST_OVF || o.status == LCB_ST_VOTE_OVF)) d->compactPoolOvf++;
             A.tried[(size_t)s] |= (uint8_t)(1u << mode);
-            // The next variant. The ladder is compact -> wide -> big -> huge by capacity of instances and vote table, but the
-            // PATH capacity is the other way round between the first two: the wide variant keeps its path set in LDS (4096
-            // vertices), the compact one in HBM (65 536). A long path with few instances (long blocks of few genomes, k = 25)
-            // that started in the wide variant therefore goes back to the compact one - unless it already holds more
-            // instances than half the compact pool (the repeat-rich seeds of config 3: thousands of instances AND > 4096
-            // pushes; they would crawl through the compact variant only to overflow its pool) - the rest goes on to big.
-            int nextMode = mode < 3 ? mode + 1 : 3;
-            if (mode == 1 && o.status == LCB_ST_PATH_OVF && !(A.tried[(size_t)s] & 1u) && o.poolInst * 2 <= d->compactIC()) nextMode = 0;
-            else if (mode == 0 && o.status == LCB_ST_PATH_OVF && d->ws[0].pathCap < d->o.path_cap_max && o.poolInst * 2 <= d->compactIC()) {
-                // a long path of few instances: the compact slots get a larger path set (runToCompletion) and the seed runs there again
+            const int nextMode = nextVariant(mode, o.status, A.tried[(size_t)s], o.poolInst, d->compactIC(), d->ws[0].pathCap < d->o.path_cap_max);
+            if (nextMode == GROW_COMPACT_PATH) {
+                // the compact slots get a larger path set (runToCompletion) and the seed runs there again
                 A.growCompactPath = true;
                 A.tried[(size_t)s] &= (uint8_t)~1u;
                 A.todo[0].push_back(s);
                 continue;
             }
-            else if (mode == 0 && o.status == LCB_ST_PATH_OVF) nextMode = 2;
-            else if (mode == 0 && (A.tried[(size_t)s] & 2u)) nextMode = 2;
             if (mode == 3) hugeOverflow = true; else setHint(d, A.seeds[s], (uint8_t)nextMode);
             A.todo[nextMode].push_back(s);
         }
@@ -1054,9 +1143,10 @@ bool gatherBatch(lcb_device_impl* d, ProcAcc& A, const std::vector<int64_t>& lis
     return hugeOverflow;
 }
 
-// Launches (and waits for) everything that is still to do, variant by variant, until no seed is left.
+// Launches (and waits for) everything that is still to do, variant by variant, until no seed is left: on the first set of host buffers.
 void runToCompletion(lcb_device_impl* d, ProcAcc& A)
 {
+    HostBufs& B = d->bufs;
     for (int round = 0; ; round++) {
         int mode = -1;
         for (int m = 0; m < 4; m++) if (!A.todo[m].empty()) { mode = m; break; }
@@ -1068,11 +1158,12 @@ void runToCompletion(lcb_device_impl* d, ProcAcc& A)
         bool hugeOverflow = false;
         for (size_t at = 0; at < list.size(); at += d->batchCap) {
             const uint32_t m = (uint32_t)std::min<size_t>(list.size() - at, d->batchCap);
-            fillSeeds(d, A, list, at, m);
+            fillSeeds(B, A, list, at, m);
             if (mode >= 2) d->bigRetries += m;
             const bool screen = !d->stats && m >= d->o.screen_min;
-            d->launch(ws, m, screen);
-            hugeOverflow = gatherBatch(d, A, list, at, m, screen, mode) || hugeOverflow;
+            d->launch(ws, B, m, screen, A.wantFp);
+            d->finishLaunch(ws, B, m);
+            hugeOverflow = gatherBatch(d, B, A, list, at, m, screen, mode) || hugeOverflow;
         }
         if (mode == 0 && d->compactSmall && d->compactAuto && d->compactDone + d->compactPoolOvf >= 65536 && d->compactPoolOvf * 8 > d->compactDone + d->compactPoolOvf) {
             // a safeguard behind the choice by the input: more than an eighth of the live seeds outgrow the small pools (and run again in the wide variant, one
@@ -1088,13 +1179,13 @@ void runToCompletion(lcb_device_impl* d, ProcAcc& A)
             c.pathCap = (uint32_t)std::min<uint64_t>((uint64_t)c.pathCap * 4, d->o.path_cap_max); c.bodyCap = c.pathCap / 2;
             d->allocWork(c);
             d->compactPathGrown++;
-        } else if (A.arenaOvf && d->arenaCap < (1ull << 26)) {
+        } else if (A.arenaOvf && B.arenaCap < (1ull << 26)) {
             // Seeds that found the result arena full were computed for nothing: it is enlarged at the first sign (config 3 lost
             // 10 % of its kernel time to second and third launches of the same seeds with a fixed arena of 2^20 instances)
-            d->allocArena(d->arenaCap * 4);
+            d->allocArena(B, B.arenaCap * 4);
             d->arenaGrown++;
         } else
-        if (!A.todo[mode].empty() && mode < 3 && A.todo[mode].size() == list.size()) d->allocArena(d->arenaCap * 4);   // not even one batch fitted
+        if (!A.todo[mode].empty() && mode < 3 && A.todo[mode].size() == list.size()) d->allocArena(B, B.arenaCap * 4);   // not even one batch fitted
         A.arenaOvf = 0;
         if (hugeOverflow) {
             // (statuses are per seed; growing everything keeps the logic simple and this path is rare)
@@ -1102,34 +1193,32 @@ void runToCompletion(lcb_device_impl* d, ProcAcc& A)
             // (the reference's vectors are unbounded, path.h:683-685: the huge variant's capacities double until the memory is gone -
             // pool indices are 32-bit there; from 2^16 instances on the number of slots halves with every doubling)
             if (b.instCap >= (1u << 26)) throw LcbError("a seed needs more than 2^26 path instances: not supported by the device");
-            if (d->arenaCap < (1ull << 30)) d->allocArena(d->arenaCap * 4);
+            if (B.arenaCap < (1ull << 30)) d->allocArena(B, B.arenaCap * 4);
             b.pathCap *= 2; b.bodyCap *= 2; b.instCap *= 2; b.voteCap *= 2; b.bestCap *= 2;
             if (b.instCap > 65536 && b.nSlots > 4) b.nSlots /= 2;
             d->allocWork(b);
-        } else if (mode == 3 && !A.todo[3].empty()) d->allocArena(d->arenaCap * 4);
+        } else if (mode == 3 && !A.todo[3].empty()) d->allocArena(B, B.arenaCap * 4);
     }
     if (A.n >= 64 && !d->o.start_mode) d->recentBigFrac = (double)A.neededBig / (double)A.n;
 }
 
-void accLayout(ProcAcc& A, std::vector<uint64_t>& offsets, std::vector<lcb_instance>& inst, std::vector<uint64_t>* fpOffsets, std::vector<lcb_fp>* fpOut)
+// per-seed pieces in arrival order (seed s: cnt[s] elements of flat from at[s]) -> seed order: out and offsets[n + 1]
+template <class T_>
+void layoutBySeed(int64_t n, const std::vector<T_>& flat, const std::vector<uint64_t>& at, const std::vector<uint32_t>& cnt, std::vector<uint64_t>& offsets, std::vector<T_>& out)
 {
-    const int64_t n = A.n;
     offsets.assign((size_t)n + 1, 0);
     uint64_t total = 0;
-    for (int64_t s = 0; s < n; s++) { offsets[(size_t)s] = total; total += A.cnt[(size_t)s]; }
+    for (int64_t s = 0; s < n; s++) { offsets[(size_t)s] = total; total += cnt[(size_t)s]; }
     offsets[(size_t)n] = total;
-    inst.resize((size_t)total);
+    out.resize((size_t)total);
     for (int64_t s = 0; s < n; s++)
-        if (A.cnt[(size_t)s]) memcpy(inst.data() + offsets[(size_t)s], A.flat.data() + A.flatOff[(size_t)s], (size_t)A.cnt[(size_t)s] * sizeof(lcb_instance));
-    if (A.wantFp) {
-        fpOffsets->assign((size_t)n + 1, 0);
-        uint64_t tf = 0;
-        for (int64_t s = 0; s < n; s++) { (*fpOffsets)[(size_t)s] = tf; tf += A.fpCnt[(size_t)s]; }
-        (*fpOffsets)[(size_t)n] = tf;
-        fpOut->resize((size_t)tf);
-        for (int64_t s = 0; s < n; s++)
-            if (A.fpCnt[(size_t)s]) memcpy(fpOut->data() + (*fpOffsets)[(size_t)s], A.fpFlat.data() + A.fpAt[(size_t)s], (size_t)A.fpCnt[(size_t)s] * sizeof(lcb_fp));
-    }
+        if (cnt[(size_t)s]) memcpy(out.data() + offsets[(size_t)s], flat.data() + at[(size_t)s], (size_t)cnt[(size_t)s] * sizeof(T_));
+}
+
+void accLayout(ProcAcc& A, std::vector<uint64_t>& offsets, std::vector<lcb_instance>& inst, std::vector<uint64_t>* fpOffsets, std::vector<lcb_fp>* fpOut)
+{
+    layoutBySeed(A.n, A.flat, A.flatOff, A.cnt, offsets, inst);
+    if (A.wantFp) layoutBySeed(A.n, A.fpFlat, A.fpAt, A.fpCnt, *fpOffsets, *fpOut);
 }
 
 }  // namespace
@@ -1141,13 +1230,10 @@ void lcb_device_process_impl(lcb_device* h, const lcb_seed* seeds, int64_t n, st
     lcb_device_impl* d = h->impl;
     d->use();
     inst.clear();
-    d->wantFp = fpOffsets != nullptr && fpOut != nullptr;
     ProcAcc A;
-    accInit(d, A, seeds, n, view, bestScore, ctr, perSeedCtr, d->wantFp);
-    try { runToCompletion(d, A); } catch (...) {
-        d->wantFp = false; throw; }
+    accInit(d, A, seeds, n, view, bestScore, ctr, perSeedCtr, fpOffsets != nullptr && fpOut != nullptr);
+    runToCompletion(d, A);
     accLayout(A, offsets, inst, fpOffsets, fpOut);
-    d->wantFp = false;
 }
 
 // ---- a call whose first launch runs while the host is still busy with something else --------------------------------------
@@ -1169,7 +1255,7 @@ bool lcb_device_process_begin_impl(lcb_device* h, const lcb_seed* seeds, int64_t
 {
     lcb_device_impl* d = h->impl;
     if (d->stats || d->async || n <= 0 || n > (int64_t)d->batchCap) return false;
-    if (d->hDbg || d->seedTrace || d->forceProf) return false;     // (the instrumented variants share one profile buffer)
+    if (d->instrumented()) return false;     // (the instrumented variants share one profile buffer)
     d->use();
     std::unique_ptr<lcb_async_call> c(new lcb_async_call());
     c->A.ownSeeds.assign(seeds, seeds + n);
@@ -1178,14 +1264,10 @@ bool lcb_device_process_begin_impl(lcb_device* h, const lcb_seed* seeds, int64_t
     c->list.swap(c->A.todo[c->mode]);
     c->m = (uint32_t)c->list.size();
     if (c->m) {
-        d->wantFp = true;
-        d->swapBufs();
-        fillSeeds(d, c->A, c->list, 0, c->m);
+        fillSeeds(d->bufsEarly, c->A, c->list, 0, c->m);
         c->screen = c->m >= d->o.screen_min;
         if (c->mode >= 2) d->bigRetries += c->m;
-        try { d->launch(d->ws[c->mode], c->m, c->screen, false); } catch (...) { d->swapBufs(); d->wantFp = false; throw; }
-        d->swapBufs();
-        d->wantFp = false;
+        d->launch(d->ws[c->mode], d->bufsEarly, c->m, c->screen, true);
         c->launched = true;
     }
     d->async = c.release();
@@ -1201,20 +1283,12 @@ void lcb_device_process_end_impl(lcb_device* h, std::vector<uint64_t>& offsets, 
     d->async = nullptr;
     d->use();
     inst.clear();
-    d->wantFp = true;
     if (c->launched) {
-        d->swapBufs();
-        try {
-            WorkSet& ws = d->ws[c->mode];
-            const uint32_t grid = c->m < ws.nSlots ? c->m : ws.nSlots;
-            d->finishLaunch(ws, c->m, grid, false, d->ev2, d->ev3);
-            gatherBatch(d, c->A, c->list, 0, c->m, c->screen, c->mode);
-        } catch (...) { d->swapBufs(); d->wantFp = false; throw; }
-        d->swapBufs();
+        d->finishLaunch(d->ws[c->mode], d->bufsEarly, c->m);
+        gatherBatch(d, d->bufsEarly, c->A, c->list, 0, c->m, c->screen, c->mode);
     }
     runToCompletion(d, c->A);
     accLayout(c->A, offsets, inst, &fpOffsets, &fpOut);
-    d->wantFp = false;
 }
 
 
@@ -1228,10 +1302,9 @@ void lcb_device_process_end_impl(lcb_device* h, std::vector<uint64_t>& offsets, 
 // kernel time of a finished batch goes into the device's totals; the lane is idle afterwards
 static void lcb_lane_retire(lcb_device_impl* d, SideLane& L)
 {
-    float ms = 0;
     // (a lane runs the wide kernel on one stream and the big kernel on the other)
-    if (L.ranW) { HIP_CHECK(hipEventSynchronize(L.w1)); HIP_CHECK(hipEventElapsedTime(&ms, L.w0, L.w1)); d->kernelMs += ms; d->sideKernelMs += ms; d->launches++; d->noteSpan(L.w0, L.w1); d->modeMs[1] += ms; d->modeLaunches[1]++; }
-    if (L.ranB) { HIP_CHECK(hipEventSynchronize(L.b1)); HIP_CHECK(hipEventElapsedTime(&ms, L.b0, L.b1)); d->kernelMs += ms; d->sideKernelMs += ms; d->launches++; d->noteSpan(L.b0, L.b1); d->modeMs[2] += ms; d->modeLaunches[2]++; }
+    if (L.ranW) { HIP_CHECK(hipEventSynchronize(L.w1)); d->accountKernel(1, L.w0, L.w1, true); }
+    if (L.ranB) { HIP_CHECK(hipEventSynchronize(L.b1)); d->accountKernel(2, L.b0, L.b1, true); }
     L.busy = L.released = L.ranW = L.ranB = false;
 }
 
@@ -1259,7 +1332,7 @@ static void lcb_device_drain_lanes(lcb_device_impl* d)
 int lcb_device_side_begin_impl(lcb_device* h, const lcb_seed* seeds, const uint32_t* view, int64_t n, int nViews, const LcbViewMark* marks, int64_t nMarks)
 {
     lcb_device_impl* d = h->impl;
-    if (d->lanes.empty() || d->stats || d->o.start_mode || n <= 0 || d->hDbg || d->seedTrace || d->forceProf) return -1;
+    if (d->lanes.empty() || d->stats || d->o.start_mode || n <= 0 || d->instrumented()) return -1;
     d->use();
     int lane = -1;
     for (size_t l = 0; l < d->lanes.size() && lane < 0; l++) if (!d->lanes[l].busy) lane = (int)l;
@@ -1279,14 +1352,9 @@ int lcb_device_side_begin_impl(lcb_device* h, const lcb_seed* seeds, const uint3
     uint32_t* listW = L.hList; uint32_t* listB = L.hList + L.cap;
     L.seeds.assign(seeds, seeds + n);
     for (int64_t i = 0; i < n; i++) {
-        L.hSeeds[i].vid = seeds[i].vid; L.hSeeds[i].ch = seeds[i].ch; L.hSeeds[i].view = view ? view[i] : 0u; L.hSeeds[i].pad = 0;
+        L.hSeeds[i] = kernelSeed(seeds[i], view ? view[i] : 0u);
         L.hOut[i].status = LCB_ST_PENDING;
-        uint8_t mode = 1;
-        if (!d->modeHint.empty()) {
-            const uint64_t key = hintKey(seeds[i]);
-            const uint32_t hb = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 48);
-            if ((d->hintBits[hb >> 6] >> (hb & 63)) & 1ull) { auto it = d->modeHint.find(key); if (it != d->modeHint.end()) mode = it->second; }
-        }
+        const uint8_t mode = hintOf(d, seeds[i], 1);
         if (mode >= 3) L.hOut[i].status = LCB_ST_ABORTED;           // the huge variant does not run here: no result
         // (hint 0: a path too long for the wide variant's LDS path set - a lane has no compact kernel, so it runs in the big one)
         else if ((mode == 2 || mode == 0) && d->o.side_big_cap != 0xFFFFFFFFu && nB >= d->o.side_big_cap) L.hOut[i].status = LCB_ST_ABORTED;   // more heavy speculation than the lane's cap: no result (the plan's order is the order of need)
@@ -1300,18 +1368,9 @@ int lcb_device_side_begin_impl(lcb_device* h, const lcb_seed* seeds, const uint3
     LcbTables T = d->T;
     T.viewTab = L.views.tab;
     auto start = [&](WorkSet& w, hipStream_t q, hipEvent_t e0, hipEvent_t e1, uint32_t m, uint32_t* list, uint32_t ticketWord, uint32_t countWord) {
-        LcbWork W;
-        W.base = w.base; W.slotBytes = w.slotBytes; W.pathCap = w.pathCap; W.bodyCap = w.bodyCap; W.bestCap = w.bestCap; W.instCap = w.instCap; W.voteCap = w.voteCap;
-        W.cursor = L.dCtl + ticketWord; W.cursorBase = 0; W.live = list; W.nLive = L.dCtl + countWord;
-        W.arenaCursor = (unsigned long long*)(L.dCtl + 2); W.arenaBase = 0; W.fpCursor = (unsigned long long*)(L.dCtl + 4); W.fpBase = 0;
-        W.ctr = nullptr; W.dbg = nullptr; W.abort = L.dCtl + 8;
-        const uint32_t grid = m < w.nSlots ? m : w.nSlots;
+        const LcbWork W = makeWork(w, L.dCtl, ticketWord, list, L.dCtl + countWord, L.dCtl + 8, nullptr, nullptr);
         HIP_CHECK(hipEventRecord(e0, q));
-        if (w.mode == 2 && d->seg) hipLaunchKernelGGL((lcb_process_kernel<2, false, LCB_NW_BIG, false, true>), dim3(grid), dim3(64 * LCB_NW_BIG), 0, q, T, d->KP, L.hSeeds, (uint32_t)n, W, L.hOut, L.hArena, L.arenaCap, L.hFp, L.arenaCap);
-        else if (w.mode == 2) hipLaunchKernelGGL((lcb_process_kernel<2, false, LCB_NW_BIG, false, false>), dim3(grid), dim3(64 * LCB_NW_BIG), 0, q, T, d->KP, L.hSeeds, (uint32_t)n, W, L.hOut, L.hArena, L.arenaCap, L.hFp, L.arenaCap);
-        else if (d->seg) hipLaunchKernelGGL((lcb_process_kernel<1, false, LCB_NW_WIDE, false, true>), dim3(grid), dim3(64 * LCB_NW_WIDE), 0, q, T, d->KP, L.hSeeds, (uint32_t)n, W, L.hOut, L.hArena, L.arenaCap, L.hFp, L.arenaCap);
-        else hipLaunchKernelGGL((lcb_process_kernel<1, false, LCB_NW_WIDE, false, false>), dim3(grid), dim3(64 * LCB_NW_WIDE), 0, q, T, d->KP, L.hSeeds, (uint32_t)n, W, L.hOut, L.hArena, L.arenaCap, L.hFp, L.arenaCap);
-        HIP_CHECK(hipGetLastError());
+        launchProcess(w.mode, FLAVOUR_PLAIN, d->seg, lcb_device_impl::gridOf(w, m), q, T, d->KP, W, LaunchIo{L.hSeeds, (uint32_t)n, L.hOut, L.hArena, L.arenaCap, L.hFp, L.arenaCap});
         HIP_CHECK(hipEventRecord(e1, q));
         d->modeSeeds[w.mode] += m;
     };
@@ -1343,10 +1402,7 @@ int lcb_device_side_poll_impl(lcb_device* h, int lane, int64_t k, bool wait, std
     std::atomic_thread_fence(std::memory_order_acquire);
     const LcbSeedOut o = L.hOut[k];
     if (o.status == LCB_ST_OK) {
-        const uint4* src = L.hArena + o.arenaOff;
-        for (uint32_t e = 0; e < o.nInst; e++) inst.push_back(lcb_instance{src[e].x, src[e].y, src[e].z, src[e].w});
-        const LcbFpOut* fs = L.hFp + o.fpOff;
-        for (uint32_t e = 0; e < o.nFp; e++) fp.push_back(lcb_fp{d->plan.toHost(fs[e].lo), d->plan.toHost(fs[e].hi)});
+        appendResult(d->plan, o, L.hArena, L.hFp, inst, fp);
         return 1;
     }
     if (o.status == LCB_ST_DIST_OVF) throw LcbError("a path longer than 2^31 bp is not supported");
