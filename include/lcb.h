@@ -274,6 +274,39 @@ int64_t lcb_device_enumerate_seeds(lcb_device* d, lcb_seed** out, lcb_seed_stats
  * resolve_pos does not fit 32 bits or a resolve_chr 24. Seeds with equal keys keep their order. */
 int lcb_device_sort_seeds(lcb_device* d, lcb_seed* seeds, int64_t n);
 
+/* ---- tables on the device: where lcb_device_create* computes the tables that are functions of the loaded graph. LCB_TABLES_HOST is
+ * lcb_device_create_ex: look-ahead windows, occurrence lists and occurrence records are made by host threads and uploaded (about 30 B
+ * per occurrence). LCB_TABLES_DEVICE uploads only the four per-position arrays (10 B per occurrence) and the segment plan, and
+ * computes the rest - the same bytes - with HIP kernels: one lane per position for the windows, a count and a scan for the lists, a
+ * stable LSD radix sort of (|id|, position) for the order inside them, a gather for the records (DESIGN.md has the kernels, the
+ * order argument and the memory formula). The build's temporaries are released before the rest of the device is made; a request
+ * that does not fit what the device reports free fails up front with both numbers in the message. */
+#define LCB_TABLES_HOST 0
+#define LCB_TABLES_DEVICE 1
+typedef struct {            /* output only; may be NULL */
+    int64_t positions, vertices;
+    int32_t sort_passes, sort_passes_skipped;
+    uint64_t upload_bytes, device_bytes;   /* H2D bytes of the table step; peak of the build's temporaries */
+    double upload_ms, window_ms, csr_ms, sort_ms, gather_ms;   /* device phases hipEvent-timed; upload = wall time of the synchronous copies */
+} lcb_table_stats;
+/* On the host route `stats` reports positions, vertices, upload_bytes and upload_ms, and zeros elsewhere. NULL on error. */
+lcb_device* lcb_device_create_tables(const lcb_graph* g, const lcb_params* p, int device_ordinal, const lcb_device_opts* opts /* may be NULL */,
+                                     int tables, lcb_table_stats* stats);
+/* Test seam, like lcb_process_seeds_fp: copies n elements [first, first + n) of one table of the device to the host. Per-position
+ * tables are addressed by dense HOST position (the call translates to the device's flat indices and splits at segment boundaries);
+ * LCB_TABLE_OCC_START is always widened to uint64_t; LCB_TABLE_OCC_REC has 16-byte elements in CSR order. out_bytes must be n times the
+ * element size; a wrong id, range or out_bytes is an error that names the values. */
+#define LCB_TABLE_POS_ID 0       /* int32_t  [positions] */
+#define LCB_TABLE_POS_POS 1      /* uint32_t [positions] */
+#define LCB_TABLE_POS_WIN 2      /* uint32_t [positions] */
+#define LCB_TABLE_POS_CH 3       /* uint8_t  [positions] */
+#define LCB_TABLE_POS_REV_CH 4   /* uint8_t  [positions] */
+#define LCB_TABLE_OCC_START 5    /* uint64_t [vertices + 1] */
+#define LCB_TABLE_OCC_REC 6      /* 4 x uint32_t [positions] */
+#define LCB_TABLE_CHR_LO_HI 7    /* 2 x uint32_t [chromosomes] */
+#define LCB_TABLE_SEG_BASE 8     /* uint64_t [32] */
+int lcb_device_table_read(lcb_device* d, int table, uint64_t first, uint64_t n, void* out, uint64_t out_bytes);
+
 /* THE HOT PATH: ProcessVertex::Process (blocksfinder.h:228-310) for a batch of seeds, each against the
  * device's current `used` state, one seed per workgroup (wavefront 0 runs the seed, the others share its look-ahead votes). offsets has n+1 entries; the instances of seed
  * i are inst[offsets[i] .. offsets[i+1]). Returns LCB_OK, or LCB_ERR (e.g. inst_cap too small: the needed

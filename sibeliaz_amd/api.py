@@ -112,6 +112,19 @@ class SeedStats(C.Structure):
                 ("device_bytes", C.c_uint64)] + [(n, C.c_double) for n in ("count_ms", "fill_ms", "sort_ms", "copy_ms")]
 
 
+class TableStats(C.Structure):
+    """lcb_table_stats: what lcb_device_create_tables reports."""
+    _fields_ = [("positions", C.c_int64), ("vertices", C.c_int64), ("sort_passes", C.c_int32), ("sort_passes_skipped", C.c_int32),
+                ("upload_bytes", C.c_uint64), ("device_bytes", C.c_uint64)] + [(n, C.c_double) for n in ("upload_ms", "window_ms", "csr_ms", "sort_ms", "gather_ms")]
+
+
+TABLE_ROUTES = {"host": 0, "device": 1}      # LCB_TABLES_HOST / LCB_TABLES_DEVICE
+# lcb_device_table_read: name -> (LCB_TABLE_* id, dtype of an element)
+OCC_REC_DTYPE = np.dtype([("g", "<u4"), ("cw", "<u4"), ("pos", "<u4"), ("id", "<i4")])
+TABLES = {"pos_id": (0, np.dtype("<i4")), "pos_pos": (1, np.dtype("<u4")), "pos_win": (2, np.dtype("<u4")), "pos_ch": (3, np.dtype("u1")), "pos_rev_ch": (4, np.dtype("u1")),
+          "occ_start": (5, np.dtype("<u8")), "occ_rec": (6, OCC_REC_DTYPE), "chr_lo_hi": (7, np.dtype([("lo", "<u4"), ("hi", "<u4")])), "seg_base": (8, np.dtype("<u8"))}
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in COUNTER_NAMES]
 
@@ -132,6 +145,7 @@ EXPORTS = [
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
     "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan", "lcb_device_enumerate_seeds", "lcb_device_sort_seeds", "lcb_gpus_device",
+    "lcb_device_create_tables", "lcb_device_table_read",
 ]
 
 
@@ -180,6 +194,9 @@ def load_library():
     L.lcb_device_create.argtypes = [vp, C.POINTER(Params), C.c_int]
     L.lcb_device_create_ex.restype = vp
     L.lcb_device_create_ex.argtypes = [vp, C.POINTER(Params), C.c_int, C.POINTER(DeviceOpts)]
+    L.lcb_device_create_tables.restype = vp
+    L.lcb_device_create_tables.argtypes = [vp, C.POINTER(Params), C.c_int, C.POINTER(DeviceOpts), C.c_int, C.POINTER(TableStats)]
+    L.lcb_device_table_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_uint64]
     L.lcb_device_mode_seeds.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "lcb_device_mode_time"):      # (an A/B library of an earlier round, LCB_LIB, lacks it)
         L.lcb_device_mode_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
@@ -343,9 +360,13 @@ class JunctionStorage:
 class Device:
     """One MI355X holding the tables and the `used` bitmap in HBM."""
 
-    def __init__(self, storage, params, ordinal=0, **opts):
+    def __init__(self, storage, params, ordinal=0, tables="host", **opts):
         """opts: fields of lcb_device_opts (compact_slots, wide_slots, big_slots, path_cap, wide_path_cap, max_views, batch,
-        wide_threshold, start_mode, screen_min)."""
+        wide_threshold, start_mode, screen_min). tables: "host" (the default: windows, occurrence lists and records are made by host
+        threads and uploaded) or "device" (computed on the GPU from the per-position arrays: lcb_device_create_tables); the tables are
+        the same bytes either way. table_stats: lcb_table_stats as a dict."""
+        if tables not in TABLE_ROUTES:
+            raise LcbError("tables=%r: \"host\" or \"device\"" % (tables,))
         self.L = load_library()
         self.storage = storage
         self.params = params
@@ -354,9 +375,24 @@ class Device:
             if not hasattr(o, k):
                 raise TypeError("unknown device option %r" % k)
             setattr(o, k, int(v))
-        self.h = self.L.lcb_device_create_ex(storage.h, C.byref(params), ordinal, C.byref(o))
+        st = TableStats()
+        self.h = self.L.lcb_device_create_tables(storage.h, C.byref(params), ordinal, C.byref(o), TABLE_ROUTES[tables], C.byref(st))
         if not self.h:
             raise _err(self.L)
+        self.tables = tables
+        self.table_stats = {f: getattr(st, f) for f, _ in TableStats._fields_}
+
+    def read_table(self, name):
+        """One table of the device as a numpy array (lcb_device_table_read; a test seam): pos_id, pos_pos, pos_win, pos_ch, pos_rev_ch by
+        dense host position, occ_start (always 64-bit), occ_rec (OCC_REC_DTYPE, CSR order), chr_lo_hi, seg_base."""
+        if name not in TABLES:
+            raise LcbError("read_table(%r): one of %s" % (name, ", ".join(sorted(TABLES))))
+        tid, dtype = TABLES[name]
+        n = {"occ_start": self.table_stats["vertices"] + 1, "chr_lo_hi": int(self.L.lcb_graph_n_chr(self.storage.h)), "seg_base": 32}.get(name, self.table_stats["positions"])
+        out = np.zeros(n, dtype=dtype)
+        if self.L.lcb_device_table_read(self.h, tid, 0, n, out.ctypes.data if n else None, n * dtype.itemsize):
+            raise _err(self.L)
+        return out
 
     def mode_seeds(self):
         """Seeds handed to the (compact, wide, big, huge) kernel variants since creation."""

@@ -193,6 +193,22 @@ lcb_device* lcb_device_create_ex(const lcb_graph* g, const lcb_params* p, int de
     return lcb_device_create_impl(g, p, device_ordinal, opts);
     LCB_CATCH(nullptr)
 }
+lcb_device* lcb_device_create_tables(const lcb_graph* g, const lcb_params* p, int device_ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats)
+{
+    LCB_TRY
+    if (!g || !p) throw LcbError("lcb_device_create_tables: null argument");
+    checkAbi(nullptr, opts);
+    return lcb_device_create_tables_impl(g, p, device_ordinal, opts, tables, stats);
+    LCB_CATCH(nullptr)
+}
+int lcb_device_table_read(lcb_device* d, int table, uint64_t first, uint64_t n, void* out, uint64_t out_bytes)
+{
+    LCB_TRY
+    LCB_NEED(d && (out || n == 0), "lcb_device_table_read");
+    lcb_device_table_read_impl(d, table, first, n, out, out_bytes);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
 int lcb_device_mode_seeds(lcb_device* d, int64_t counts[4])
 {
     LCB_TRY

@@ -42,6 +42,8 @@
         if (e_ != hipSuccess) throw LcbError(std::string(#x) + " failed: " + hipGetErrorString(e_)); \
     } while (0)
 
+static double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 // MODE 0/1/2/3 = compact / wide / big / huge (lcb_kernel.h): where the per-path instance pool and vote table live.
 // NW wavefronts per workgroup: wave 0 runs the per-seed algorithm, the rest share the votes.
 #ifndef LCB_NW_WIDE
@@ -257,6 +259,8 @@ struct lcb_device_impl {
     LcbKParams KP{};
     LcbSegPlan plan;                             // host positions <-> (segment, g) of the device tables
     bool seg = false;                            // the SEG instantiations of the kernels run (several segments)
+    int tables = LCB_TABLES_HOST;                // where posWin, occStart and occRec were computed (createTables / tables.hip)
+    lcb_table_stats tableStats{};                // ... and what that cost
     uint32_t* dUsed = nullptr;                   // the live bitmap
     size_t usedWords = 0;                        // its words (a multiple of the page size)
     uint32_t nPages = 0;
@@ -351,7 +355,9 @@ struct lcb_device_impl {
     T_* upload(const T_* src, size_t n)
     {
         T_* d = devAlloc<T_>((n ? n : 1) * sizeof(T_));
+        const double t0 = nowMs();
         if (n) HIP_CHECK(hipMemcpy(d, src, n * sizeof(T_), hipMemcpyHostToDevice));
+        tableStats.upload_ms += nowMs() - t0; tableStats.upload_bytes += n * sizeof(T_);
         return d;
     }
 
@@ -361,10 +367,12 @@ struct lcb_device_impl {
     T_* uploadSeg(const T_* src, const LcbSegPlan& pl)
     {
         T_* dv = devAlloc<T_>((size_t)(pl.devPositions ? pl.devPositions : 1) * sizeof(T_));
+        const double t0 = nowMs();
         for (uint32_t sg = 0; sg < pl.nSeg(); sg++) {
             const uint64_t a = pl.segStart[sg], b = pl.segStart[sg + 1];
             if (b > a) HIP_CHECK(hipMemcpy(dv + pl.segDev[sg], src + a, (size_t)(b - a) * sizeof(T_), hipMemcpyHostToDevice));
         }
+        tableStats.upload_ms += nowMs() - t0; tableStats.upload_bytes += (pl.segStart[pl.nSeg()] - pl.segStart[0]) * sizeof(T_);
         return dv;
     }
 
@@ -526,6 +534,33 @@ void createOptions(lcb_device_impl* d, uint32_t nCu)
     if (o.path_cap & (o.path_cap - 1)) throw LcbError("lcb_device_opts.path_cap must be a power of two");
 }
 
+// The device route of the tables (LCB_TABLES_DEVICE; tables.hip): only the four per-position arrays go up; posWin,
+// occStart and occRec - functions of them - are computed there. The host's `win` and `rec` vectors are never built.
+void createTablesOnDevice(lcb_device_impl* d)
+{
+    static const char* fn = "lcb_device_create_tables";
+    const lcb_graph* g = d->g;
+    const LcbSegPlan& plan = d->plan;
+    const uint64_t D = plan.devPositions ? plan.devPositions : 1, V1 = (uint64_t)g->nVertex + 1;
+    lcb_tables_need_impl(fn, D * 14 + V1 * (d->seg ? 8 : 4), "the per-position tables of " + std::to_string(g->nPos()) + " positions (14 bytes each) and the lists of " + std::to_string(g->nVertex) + " vertices");
+    d->T.posId = d->uploadSeg(g->posId.data(), plan);
+    d->T.posPos = d->uploadSeg(g->posPos.data(), plan);
+    d->T.posCh = d->uploadSeg(g->posCh.data(), plan);
+    d->T.posRevCh = d->uploadSeg(g->posRevCh.data(), plan);
+    uint32_t* win = d->devAlloc<uint32_t>((size_t)D * sizeof(uint32_t));
+    d->T.posWin = win;
+    LcbTableJob job;
+    job.fn = fn; job.stream = (void*)d->stream; job.g = g; job.plan = &plan; job.seg = d->seg; job.maxBranch = (uint32_t)d->p.max_branch;
+    job.posId = d->T.posId; job.posPos = d->T.posPos; job.segBase = d->T.segBase; job.posWin = win;
+    if (d->seg) { uint64_t* os = d->devAlloc<uint64_t>((size_t)V1 * 8); d->T.occStart64 = os; d->T.occStart32 = nullptr; job.occStart = os; }
+    else { uint32_t* os = d->devAlloc<uint32_t>((size_t)V1 * 4); d->T.occStart32 = os; d->T.occStart64 = nullptr; job.occStart = os; }
+    job.owner = d;
+    job.alloc = [](void* o, size_t bytes) { return (void*)((lcb_device_impl*)o)->devAlloc<uint8_t>(bytes); };
+    job.drop = [](void* o, void* p) { uint8_t* q = (uint8_t*)p; ((lcb_device_impl*)o)->drop(q); };
+    lcb_build_tables_impl(job, d->tableStats);
+    d->T.occRec = (const uint4*)job.occRec;
+}
+
 // the read-only tables (file header)
 void createTables(lcb_device_impl* d)
 {
@@ -538,6 +573,7 @@ void createTables(lcb_device_impl* d)
         d->T.chrLoHi = d->upload(lh.data(), lh.size());
         d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
     }
+    if (d->tables == LCB_TABLES_DEVICE) { createTablesOnDevice(d); return; }
     d->T.posId = d->uploadSeg(g->posId.data(), plan);
     d->T.posPos = d->uploadSeg(g->posPos.data(), plan);
     { const std::vector<uint32_t> win = lcb_window_table(*g, (uint32_t)d->p.max_branch); d->T.posWin = d->uploadSeg(win.data(), plan); }   // look-ahead windows (lcb_segments.h)
@@ -683,8 +719,12 @@ void createLanes(lcb_device_impl* d, uint32_t nLanes, uint32_t nCu, int prioLow)
 
 }  // namespace
 
-lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts)
+lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts) { return lcb_device_create_tables_impl(g, p, ordinal, opts, LCB_TABLES_HOST, nullptr); }
+
+lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats)
 {
+    if (tables != LCB_TABLES_HOST && tables != LCB_TABLES_DEVICE)
+        throw LcbError("lcb_device_create_tables: tables is " + std::to_string(tables) + ": LCB_TABLES_HOST (0) or LCB_TABLES_DEVICE (1)");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         throw LcbError("no HIP device available: the block-finder hot path runs only on the GPU (there is no CPU fallback)");
@@ -693,7 +733,7 @@ lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int 
     auto* d = new lcb_device_impl();
     auto* handle = new lcb_device{d};
     try {
-        d->ordinal = ordinal; d->g = g; d->p = *p;
+        d->ordinal = ordinal; d->g = g; d->p = *p; d->tables = tables;
         if (opts) d->o = *opts;
         d->use();
         hipDeviceProp_t prop;
@@ -709,6 +749,8 @@ lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int 
         for (hipEvent_t* e : {&d->bufs.e0, &d->bufs.e1, &d->bufsEarly.e0, &d->bufsEarly.e1}) *e = d->newEvent();
         const uint32_t nLanes = d->o.side_lanes == 0xFFFFFFFFu ? 0u : (d->o.side_lanes ? d->o.side_lanes : 4u);
         createTables(d);
+        d->tableStats.positions = (int64_t)g->nPos(); d->tableStats.vertices = g->nVertex;
+        if (stats) *stats = d->tableStats;
         createUsed(d, nLanes);
         createWorkSets(d);
         createHostBufs(d);
@@ -930,6 +972,50 @@ LcbSeedView lcb_device_seed_view_impl(lcb_device* h, const char* fn)
     return v;
 }
 int lcb_device_concurrency_impl(lcb_device* h) { return (int)h->impl->ws[0].nSlots; }
+
+// The test seam behind lcb_device_table_read: n elements of one table, per-position tables by dense host position.
+void lcb_device_table_read_impl(lcb_device* h, int table, uint64_t first, uint64_t n, void* out, uint64_t outBytes)
+{
+    static const char* fn = "lcb_device_table_read";
+    lcb_device_impl* d = h->impl;
+    if (d->async) throw LcbError(std::string(fn) + ": a process call is in flight on this device");
+    d->use();
+    const uint64_t P = d->g->nPos(), V1 = (uint64_t)d->g->nVertex + 1;
+    const void* base = nullptr;
+    uint64_t len = 0, elem = 0;
+    bool perPosition = false;
+    switch (table) {
+        case LCB_TABLE_POS_ID: base = d->T.posId; len = P; elem = 4; perPosition = true; break;
+        case LCB_TABLE_POS_POS: base = d->T.posPos; len = P; elem = 4; perPosition = true; break;
+        case LCB_TABLE_POS_WIN: base = d->T.posWin; len = P; elem = 4; perPosition = true; break;
+        case LCB_TABLE_POS_CH: base = d->T.posCh; len = P; elem = 1; perPosition = true; break;
+        case LCB_TABLE_POS_REV_CH: base = d->T.posRevCh; len = P; elem = 1; perPosition = true; break;
+        case LCB_TABLE_OCC_START: len = V1; elem = 8; break;
+        case LCB_TABLE_OCC_REC: base = d->T.occRec; len = P; elem = 16; break;
+        case LCB_TABLE_CHR_LO_HI: base = d->T.chrLoHi; len = d->g->nChr(); elem = 8; break;
+        case LCB_TABLE_SEG_BASE: base = d->T.segBase; len = LCB_MAX_SEG; elem = 8; break;
+        default: throw LcbError(std::string(fn) + ": table is " + std::to_string(table) + ": one of LCB_TABLE_POS_ID (0) .. LCB_TABLE_SEG_BASE (8)");
+    }
+    if (first > len || n > len - first)
+        throw LcbError(std::string(fn) + ": elements [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") of table " + std::to_string(table) + ", which has " + std::to_string(len));
+    if (outBytes != n * elem)
+        throw LcbError(std::string(fn) + ": out_bytes is " + std::to_string(outBytes) + ", " + std::to_string(n) + " elements of table " + std::to_string(table) + " are " + std::to_string(n * elem) + " bytes");
+    if (!n) return;
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    if (table == LCB_TABLE_OCC_START) {
+        if (d->T.occStart64) { HIP_CHECK(hipMemcpy(out, d->T.occStart64 + first, (size_t)n * 8, hipMemcpyDeviceToHost)); return; }
+        std::vector<uint32_t> v((size_t)n);
+        HIP_CHECK(hipMemcpy(v.data(), d->T.occStart32 + first, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; i++) ((uint64_t*)out)[i] = v[(size_t)i];
+        return;
+    }
+    if (!perPosition) { HIP_CHECK(hipMemcpy(out, (const uint8_t*)base + first * elem, (size_t)(n * elem), hipMemcpyDeviceToHost)); return; }
+    const LcbSegPlan& pl = d->plan;
+    for (uint32_t sg = 0; sg < pl.nSeg(); sg++) {      // the part of [first, first + n) inside every segment
+        const uint64_t a = std::max(first, pl.segStart[sg]), b = std::min(first + n, pl.segStart[sg + 1]);
+        if (b > a) HIP_CHECK(hipMemcpy((uint8_t*)out + (a - first) * elem, (const uint8_t*)base + (pl.segDev[sg] + (a - pl.segStart[sg])) * elem, (size_t)((b - a) * elem), hipMemcpyDeviceToHost));
+    }
+}
 
 void lcb_device_set_stats_impl(lcb_device* h, bool on) { h->impl->stats = on; }
 

@@ -4,6 +4,7 @@
 #define LCB_DEVICE_H
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "lcb_host.h"
@@ -64,6 +65,31 @@ struct LcbSeedView {                 // what the enumeration reads of a device (
 LcbSeedView lcb_device_seed_view_impl(lcb_device* d, const char* fn);     // (device.hip) fn: the caller, for the messages
 int64_t lcb_device_enumerate_seeds_impl(lcb_device* d, lcb_seed** out, lcb_seed_stats* stats);
 void lcb_device_sort_seeds_impl(lcb_device* d, lcb_seed* seeds, int64_t n);
+
+// tables.hip — the device route of device creation (LCB_TABLES_DEVICE): posWin, occStart and occRec computed on the GPU from the
+// per-position arrays that device.hip has uploaded
+struct LcbSegPlan;
+struct LcbTableJob {                 // what the build reads of a device that is being created, and where its results go (device pointers)
+    const char* fn;                  // the caller, for the messages
+    void* stream;                    // a hipStream_t
+    const lcb_graph* g;              // (sizes and chrStart only: no per-position array of the host is read)
+    const LcbSegPlan* plan;
+    bool seg;                        // the 64-bit instantiation (occStart64, u64 payloads)
+    uint32_t maxBranch;
+    const int32_t* posId;
+    const uint32_t* posPos;
+    const uint64_t* segBase;
+    uint32_t* posWin;                // [plan->devPositions], written at the positions only
+    void* occStart;                  // [nVertex + 1] uint32_t, or uint64_t if seg
+    const void* occRec = nullptr;    // OUT: [P] uint4, made by the build through alloc once the sort's second buffers are gone
+    void* (*alloc)(void* owner, size_t bytes);     // devAlloc / drop of the device that is being created
+    void (*drop)(void* owner, void* p);
+    void* owner;
+};
+void lcb_tables_need_impl(const char* fn, uint64_t bytes, const std::string& what);   // refuses a request beyond what hipMemGetInfo reports free, with both numbers
+void lcb_build_tables_impl(LcbTableJob& job, lcb_table_stats& stats);
+lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats);
+void lcb_device_table_read_impl(lcb_device* d, int table, uint64_t first, uint64_t n, void* out, uint64_t outBytes);
 
 // comm.hip — RCCL all-gather between the ranks of the round engine
 struct lcb_comm;

@@ -4,8 +4,9 @@
 // `sibeliaz` wrapper script keeps working verbatim:
 //   sibeliaz-lcb --graph <junctions> <fasta...> -k <odd> -b <int> -o <dir> -m <int> -t <int> --abundance <int> [--noseq] --chunks <int>
 // `-t` stays "host threads" (loading, seed enumeration); the GPU is chosen by the environment
-// (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag, and so is the place where the seeds are
-// enumerated (LCB_SEEDS=host, the default, or device).
+// (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag, and so are the place where the seeds are
+// enumerated (LCB_SEEDS=host, the default, or device) and the place where the device's tables are computed (LCB_TABLES=host, the
+// default, or device).
 // The block finder itself runs on the MI355X through the C ABI in include/lcb.h.
 #include <cstdio>
 #include <cstdlib>
@@ -115,6 +116,21 @@ int main(int argc, char** argv)
         return 1;
     }
     const bool deviceSeeds = seedRoute == "device";
+    // ... and where the device's tables are computed (LCB_TABLES=host, the default, or device), the same way
+    const char* tablesEnv = getenv("LCB_TABLES");
+    const std::string tableRoute = tablesEnv && *tablesEnv ? tablesEnv : "host";
+    if (tableRoute != "host" && tableRoute != "device") {
+        std::cerr << "error: LCB_TABLES is '" << tableRoute << "': it is host (the default) or device" << std::endl;
+        return 1;
+    }
+    const bool deviceTables = tableRoute == "device";
+    {
+        const char* gpus = getenv("LCB_GPUS");
+        if (deviceTables && gpus && *gpus && atoi(gpus) > 1) {
+            std::cerr << "error: LCB_TABLES=device together with LCB_GPUS=" << gpus << " is not supported: the tables are built on the device of a single-GPU run (LCB_GPUS unset or 1)" << std::endl;
+            return 1;
+        }
+    }
     lcb_graph* g = nullptr;
     lcb_device* dev = nullptr;
     lcb_gpus* set = nullptr;
@@ -147,7 +163,12 @@ int main(int argc, char** argv)
                 set = lcb_gpus_create(g, ord.data(), nGpus, &p, nullptr, 0);
                 return set != nullptr;
             }
-            dev = lcb_device_create(g, &p, devEnv && *devEnv ? atoi(devEnv) : 0);
+            lcb_table_stats ts;
+            dev = lcb_device_create_tables(g, &p, devEnv && *devEnv ? atoi(devEnv) : 0, nullptr, deviceTables ? LCB_TABLES_DEVICE : LCB_TABLES_HOST, &ts);
+            if (dev && getenv("LCB_VERBOSE"))
+                std::cerr << "lcb: device tables=" << tableRoute << " positions=" << ts.positions << " vertices=" << ts.vertices << " sort_passes=" << ts.sort_passes << " (+"
+                          << ts.sort_passes_skipped << " skipped) upload_bytes=" << ts.upload_bytes << " device_bytes=" << ts.device_bytes << " upload_ms=" << ts.upload_ms
+                          << " window_ms=" << ts.window_ms << " csr_ms=" << ts.csr_ms << " sort_ms=" << ts.sort_ms << " gather_ms=" << ts.gather_ms << std::endl;
             return dev != nullptr;
         };
         int64_t nSeeds = -1;
