@@ -195,6 +195,30 @@ int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, i
 int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget,
                        int32_t* partitions, uint64_t* need_bytes);
 
+/* ---- the graph from the FASTA files alone, on one MI355X, with no junction file: the junction finder above, whose
+ * records stay in HBM, then the abundance filter, the compaction and the per-position characters as kernels; the host parses the
+ * FASTA once, downloads 10 bytes per kept occurrence and builds the CSR. The result is the lcb_graph that lcb-mkgraph +
+ * lcb_graph_load give for the same input, k and abundance - every call that takes a graph takes it - and never depends on opts
+ * (table_log2, tile_windows, partitions and mem_budget mean what they mean in lcb_junctions_build_ex). No CPU fallback: without a GPU
+ * this fails. NULL on error (lcb_last_error); whatever way it ends, no device memory, pinned memory or file is left behind. */
+typedef struct {
+    lcb_junction_stats_ex junctions; /* the junction part (base.read_ms = parse_ms, base.write_ms = 0: nothing is written) */
+    int64_t raw_occurrences;        /* junction occurrences before the abundance filter */
+    int64_t kept_occurrences;       /* ... and behind it (= lcb_graph_n_pos) */
+    int64_t vertices;               /* = lcb_graph_n_vertices */
+    int64_t patched;                /* posCh bytes the host took from its strings: the next base is neither ACGT nor the end */
+    uint64_t download_bytes;        /* device -> host: 10 bytes per kept occurrence, 8 per chromosome (twice: first raw index, chrStart), 16 of counters */
+    uint64_t peak_device_bytes;     /* most device memory held at one time, by the build's own account (junction part included) */
+    double parse_ms;                /* host: FASTA -> names, sequences; plus the staging of the code bytes, which runs while the copies do
+                                       (junctions.base.upload_ms, hipEvent-timed, lies inside it) */
+    double count_ms, take_ms;       /* device: the counting sweep (one partition), the per-tile conversion of the records */
+    double abundance_ms, compact_ms;/* device: the counters; keep-count + scan + compaction */
+    double download_ms;             /* device -> host copies + the patch of posCh */
+    double csr_ms;                  /* host: occStart / occG / occChr */
+} lcb_graph_build_stats;
+lcb_graph* lcb_graph_build(const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, int device_ordinal,
+                           const lcb_junction_opts_ex* opts /* may be NULL */, lcb_graph_build_stats* stats /* may be NULL */);
+
 /* ---- seeds: bundle enumeration + std::sort (blocksfinder.h:461-503,517). *out is malloc'ed; free with lcb_free. */
 int64_t lcb_enumerate_seeds(const lcb_graph* g, int threads, lcb_seed** out);
 void lcb_free(void* p);

@@ -106,6 +106,13 @@ class JunctionStatsEx(C.Structure):
                 ("peak_device_bytes", C.c_uint64), ("mark_ms", C.c_double), ("passes", C.c_int64)]
 
 
+class GraphBuildStats(C.Structure):
+    """lcb_graph_build_stats: what lcb_graph_build reports."""
+    _fields_ = [("junctions", JunctionStatsEx)] + [(n, C.c_int64) for n in ("raw_occurrences", "kept_occurrences", "vertices", "patched")] + [
+        ("download_bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64)] + [
+        (n, C.c_double) for n in ("parse_ms", "count_ms", "take_ms", "abundance_ms", "compact_ms", "download_ms", "csr_ms")]
+
+
 class SeedStats(C.Structure):
     """lcb_seed_stats: what lcb_device_enumerate_seeds reports."""
     _fields_ = [("seeds", C.c_int64), ("vertices", C.c_int64), ("max_count", C.c_int64), ("sort_passes", C.c_int32), ("sort_passes_skipped", C.c_int32),
@@ -145,7 +152,7 @@ EXPORTS = [
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
     "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan", "lcb_device_enumerate_seeds", "lcb_device_sort_seeds", "lcb_gpus_device",
-    "lcb_device_create_tables", "lcb_device_table_read",
+    "lcb_device_create_tables", "lcb_device_table_read", "lcb_graph_build",
 ]
 
 
@@ -165,6 +172,8 @@ def load_library():
     L.lcb_graph_load.restype = vp
     L.lcb_graph_load.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int]
     L.lcb_graph_free.argtypes = [vp]
+    L.lcb_graph_build.restype = vp
+    L.lcb_graph_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JunctionOptsEx), C.POINTER(GraphBuildStats)]
     for f in ("lcb_graph_n_chr", "lcb_graph_n_pos", "lcb_graph_n_vertices"):
         getattr(L, f).restype = i64
         getattr(L, f).argtypes = [vp]
@@ -314,6 +323,32 @@ class JunctionStorage:
         if not self.h:
             raise _err(self.L)
         self.k = k
+
+    @classmethod
+    def build(cls, fasta_files, k, abundance=150, threads=1, device=0, partitions=None, mem_budget=None, stats=False, **opts):
+        """The same storage from the FASTA files alone, on one MI355X, with no junction file (lcb_graph_build): what
+        JunctionStorage(file written by lcb-mkgraph, fasta_files, k, threads, abundance) holds. opts: table_log2, tile_windows; partitions
+        and mem_budget as in build_junctions (None = one partition / what is free) - the storage never depends on them. stats=True:
+        -> (storage, lcb_graph_build_stats as a dict, the junction part flattened into it). No CPU fallback."""
+        o = _junction_opts(JunctionOptsEx, dict(opts, partitions=1 if partitions is None else partitions, mem_budget=mem_budget or 0),
+                           ("abi", "table_log2", "tile_windows", "partitions", "mem_budget"))
+        if isinstance(fasta_files, (str, bytes, os.PathLike)):
+            fasta_files = [fasta_files]
+        files = [os.fsencode(f) for f in fasta_files]
+        arr = (C.c_char_p * max(1, len(files)))(*files)
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.k = k
+        st = GraphBuildStats()
+        self.h = self.L.lcb_graph_build(arr, len(files), int(k), int(abundance), int(threads), int(device), C.byref(o), C.byref(st))
+        if not self.h:
+            raise _err(self.L)
+        if not stats:
+            return self
+        out = {f: getattr(st.junctions.base, f) for f, _ in JunctionStats._fields_}
+        out.update({f: getattr(st.junctions, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
+        out.update({f: getattr(st, f) for f, _ in GraphBuildStats._fields_ if f != "junctions"})
+        return self, out
 
     def close(self):
         if getattr(self, "h", None):

@@ -139,6 +139,26 @@ int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, i
     LCB_CATCH(LCB_ERR)
 }
 
+lcb_graph* lcb_graph_build(const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, int device_ordinal, const lcb_junction_opts_ex* opts,
+                           lcb_graph_build_stats* stats)
+{
+    LCB_TRY
+    const std::string fn = "lcb_graph_build";
+    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
+    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(fn + ": k must be odd and in 3..31, not " + std::to_string(k));
+    checkJunctionOpts(opts, "lcb_junction_opts_ex");
+    std::vector<std::string> fa;
+    for (int i = 0; i < n_fasta; i++) {
+        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
+        fa.push_back(fasta_files[i]);
+    }
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    return lcb_graph_build_impl(fa, k, abundance, threads, device_ordinal, opts ? *opts : o, stats);
+    LCB_CATCH(nullptr)
+}
+
 int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget, int32_t* partitions, uint64_t* need_bytes)
 {
     LCB_TRY

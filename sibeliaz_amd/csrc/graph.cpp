@@ -53,8 +53,9 @@ const ValidTable kValid;
 
 // One FASTA file: the records are located first (a '>' anywhere starts one, streamfastaparser.cpp:28-58), then parsed by all
 // threads. `header` carries over between records and files like the reference's currentHeader_ (a header line without a
-// newline at the end of the file leaves it unchanged).
-void parseFasta(const std::string& file, lcb_graph& g, size_t& record, std::string& header, int threads)
+// newline at the end of the file leaves it unchanged). grow: g.seq takes whatever records there are (lcb_graph_parse_fasta: the
+// number of chromosomes is not known yet); otherwise it has one entry per chromosome of the junction file.
+void parseFasta(const std::string& file, lcb_graph& g, size_t& record, std::string& header, int threads, bool grow)
 {
     std::vector<char> buf;
     if (!readAll(file, buf)) throw LcbError("Can't open file " + file);                 // streamfastaparser.cpp:24
@@ -92,7 +93,8 @@ void parseFasta(const std::string& file, lcb_graph& g, size_t& record, std::stri
         while (q < starts.size() && starts[q] < i) q++;                                  // '>' characters of the header line itself
     }
     const size_t nr = recStart.size();
-    if (record + nr > g.seq.size()) throw LcbError("the FASTA input has more records than the junction file has chromosomes");
+    if (grow) g.seq.resize(record + nr);
+    else if (record + nr > g.seq.size()) throw LcbError("the FASTA input has more records than the junction file has chromosomes");
     for (size_t r = 0; r < nr; r++) g.chrName.push_back(names[r]);
     std::vector<std::string> errs(nr);
 #pragma omp parallel for num_threads(threads) schedule(dynamic, 1)
@@ -118,6 +120,52 @@ void parseFasta(const std::string& file, lcb_graph& g, size_t& record, std::stri
 }
 
 }  // namespace
+
+size_t lcb_graph_parse_fasta(lcb_graph& g, const std::vector<std::string>& fasta, int threads)
+{
+    if (threads < 1) threads = 1;
+    omp_set_dynamic(0);
+    size_t record = 0;
+    std::string header;
+    for (auto& f : fasta) parseFasta(f, g, record, header, threads, true);
+    return record;
+}
+
+// CSR over |id| (replaces vertex_ + the per-vertex std::sort, junctionstorage.h:646-649): counts and slots are handed
+// out with atomics by all threads, then every vertex's short list is sorted by g, i.e. by (chr, idx).
+void lcb_graph_build_csr(lcb_graph* g, int threads)
+{
+    if (threads < 1) threads = 1;
+    omp_set_dynamic(0);
+    const uint64_t P = g->nPos();
+    g->occStart.assign((size_t)g->nVertex + 1, 0);
+#pragma omp parallel for num_threads(threads) schedule(static)
+    for (int64_t i = 0; i < (int64_t)P; i++) {
+        const int32_t id = g->posId[i];
+#pragma omp atomic
+        g->occStart[(size_t)(id < 0 ? -(int64_t)id : id) + 1]++;
+    }
+    for (size_t v = 0; v < g->nVertex; v++) g->occStart[v + 1] += g->occStart[v];
+    g->occG.resize(P); g->occChr.resize(P);
+    {
+        std::vector<uint64_t> cursor(g->occStart.begin(), g->occStart.end() - 1);
+#pragma omp parallel for num_threads(threads) schedule(static)
+        for (int64_t i = 0; i < (int64_t)P; i++) {
+            const int32_t id = g->posId[i];
+            uint64_t at;
+#pragma omp atomic capture
+            at = cursor[(size_t)(id < 0 ? -(int64_t)id : id)]++;
+            g->occG[at] = (uint64_t)i;
+        }
+    }
+#pragma omp parallel for num_threads(threads) schedule(dynamic, 4096)
+    for (int64_t v = 0; v < (int64_t)g->nVertex; v++) {
+        const uint64_t a = g->occStart[(size_t)v], b2 = g->occStart[(size_t)v + 1];
+        if (b2 - a > 1) std::sort(g->occG.begin() + (ptrdiff_t)a, g->occG.begin() + (ptrdiff_t)b2);
+        for (uint64_t j = a; j < b2; j++)
+            g->occChr[j] = (uint32_t)(std::upper_bound(g->chrStart.begin(), g->chrStart.end(), g->occG[j]) - g->chrStart.begin() - 1);
+    }
+}
 
 lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::string>& fasta, int k, int abundance, int threads)
 {
@@ -230,7 +278,7 @@ lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::
         g->seq.resize(C);
         size_t record = 0;
         std::string header;
-        for (auto& f : fasta) parseFasta(f, *g, record, header, threads);
+        for (auto& f : fasta) parseFasta(f, *g, record, header, threads, false);
         if (record != C) throw LcbError("the FASTA input has fewer records than the junction file has chromosomes");
         // ch / revCh per occurrence (junctionstorage.h:635-644)
         g->posCh.resize(P); g->posRevCh.resize(P);
@@ -246,35 +294,7 @@ lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::
             }
         }
         if (bad) throw LcbError("a junction lies beyond the end of its sequence (junction file and FASTA do not match)");
-        // CSR over |id| (replaces vertex_ + the per-vertex std::sort, junctionstorage.h:646-649): counts and slots are handed
-        // out with atomics by all threads, then every vertex's short list is sorted by g, i.e. by (chr, idx).
-        g->occStart.assign((size_t)g->nVertex + 1, 0);
-#pragma omp parallel for num_threads(threads) schedule(static)
-        for (int64_t i = 0; i < (int64_t)P; i++) {
-            const int32_t id = g->posId[i];
-#pragma omp atomic
-            g->occStart[(size_t)(id < 0 ? -(int64_t)id : id) + 1]++;
-        }
-        for (size_t v = 0; v < g->nVertex; v++) g->occStart[v + 1] += g->occStart[v];
-        g->occG.resize(P); g->occChr.resize(P);
-        {
-            std::vector<uint64_t> cursor(g->occStart.begin(), g->occStart.end() - 1);
-#pragma omp parallel for num_threads(threads) schedule(static)
-            for (int64_t i = 0; i < (int64_t)P; i++) {
-                const int32_t id = g->posId[i];
-                uint64_t at;
-#pragma omp atomic capture
-                at = cursor[(size_t)(id < 0 ? -(int64_t)id : id)]++;
-                g->occG[at] = (uint64_t)i;
-            }
-        }
-#pragma omp parallel for num_threads(threads) schedule(dynamic, 4096)
-        for (int64_t v = 0; v < (int64_t)g->nVertex; v++) {
-            const uint64_t a = g->occStart[(size_t)v], b2 = g->occStart[(size_t)v + 1];
-            if (b2 - a > 1) std::sort(g->occG.begin() + (ptrdiff_t)a, g->occG.begin() + (ptrdiff_t)b2);
-            for (uint64_t j = a; j < b2; j++)
-                g->occChr[j] = (uint32_t)(std::upper_bound(g->chrStart.begin(), g->chrStart.end(), g->occG[j]) - g->chrStart.begin() - 1);
-        }
+        lcb_graph_build_csr(g, threads);
     } catch (...) {
         delete g;
         throw;

@@ -14,16 +14,22 @@
 //   partitions the table can be built in P passes over the input, one part of the canonical k-mer space per pass (jPartition), when
 //              the whole table does not fit: a pass leaves one bit per window in a bitmap, the ids then come from a table of the
 //              junction k-mers alone, through the same tile pipeline. One partition = the single-table path above.
+//   sinks      the pipeline (junctionPipeline) has two callers. lcb_junctions_build_impl copies a tile's records to the host and writes
+//              the junction file; lcb_graph_build_impl keeps them in HBM and makes the graph of them with the kernels of
+//              lcb_graph_kernels.h - what lcb_graph_load makes of the file, without the file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "lcb_fasta.h"
+#include "lcb_graph_kernels.h"
 #include "lcb_host.h"
 #include "lcb_junction_kernels.h"
 
@@ -39,10 +45,10 @@ namespace {
 
 double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-uint32_t gridFor(uint64_t items, uint64_t perBlock)
+uint32_t gridFor(uint64_t items, uint64_t perBlock, const char* fn = "lcb_junctions_build")
 {
     const uint64_t n = std::max<uint64_t>(1, (items + perBlock - 1) / perBlock);
-    if (n > 0x7FFFFFFFull) throw LcbError("lcb_junctions_build: the input needs more workgroups than one launch has");
+    if (n > 0x7FFFFFFFull) throw LcbError(std::string(fn) + ": the input needs more workgroups than one launch has");
     return (uint32_t)n;
 }
 
@@ -62,14 +68,28 @@ struct Run {
     JRecord* hOut[2] = {nullptr, nullptr};
     FILE* f = nullptr;
     std::string part;
+    // the graph build (lcb_graph_build_impl) on top of the junction finder's: raw records, counters, the kept arrays; staging for the codes
+    uint32_t* dRawPos = nullptr;
+    int32_t* dRawId = nullptr;
+    unsigned long long *dBase = nullptr, *dRecFirst = nullptr, *dBlockKept = nullptr, *dChrStart = nullptr, *dTotals = nullptr;
+    uint32_t* dCounter = nullptr;
+    int32_t* dPosId = nullptr;
+    uint32_t* dPosPos = nullptr;
+    uint8_t *dPosCh = nullptr, *dPosRevCh = nullptr;
+    uint8_t* hStage[2] = {nullptr, nullptr};
+    std::string fn = "lcb_junctions_build";      // the call the messages name
     uint64_t budget = 0, live = 0, peak = 0;     // the run's own account of its device memory
+    uint64_t tableBytesKey = 0, tableBytesVal = 0, tileBytes[4] = {0, 0, 0, 0}, bitmapBytes = 0;   // what the pipeline holds when it returns
     ~Run()
     {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : {(void*)dCodes, (void*)dKey, (void*)dVal, (void*)dBitmap, (void*)dWslot, (void*)dOut, (void*)dCntJ, (void*)dCntF, (void*)dState})
+        for (void* p : {(void*)dCodes, (void*)dKey, (void*)dVal, (void*)dBitmap, (void*)dWslot, (void*)dOut, (void*)dCntJ, (void*)dCntF, (void*)dState, (void*)dRawPos,
+                        (void*)dRawId, (void*)dBase, (void*)dRecFirst, (void*)dBlockKept, (void*)dChrStart, (void*)dTotals, (void*)dCounter, (void*)dPosId, (void*)dPosPos,
+                        (void*)dPosCh, (void*)dPosRevCh})
             if (p) (void)hipFree(p);
         if (hState) (void)hipHostFree(hState);
         for (JRecord* p : hOut) if (p) (void)hipHostFree(p);
+        for (uint8_t* p : hStage) if (p) (void)hipHostFree(p);
         for (hipEvent_t e : {evA, evB, evCopy[0], evCopy[1]}) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (f) fclose(f);
@@ -87,7 +107,7 @@ struct Run {
         size_t freeB = 0, totalB = 0;
         HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
         if (live + bytes > budget || bytes > (uint64_t)freeB)
-            throw LcbError(std::string("lcb_junctions_build: ") + what + " needs " + std::to_string(bytes) + " bytes of device memory on top of the " + std::to_string(live) +
+            throw LcbError(fn + ": " + what + " needs " + std::to_string(bytes) + " bytes of device memory on top of the " + std::to_string(live) +
                            " in use: the budget is " + std::to_string(budget) + ", " + std::to_string((uint64_t)freeB) + " are free");
         HIP_CHECK(hipMalloc((void**)&p, bytes));
         live += bytes;
@@ -155,49 +175,53 @@ struct Writer {
 
 static_assert(sizeof(JState) + sizeof(unsigned long long) <= LCB_JUNCTION_STATE_BYTES, "the state block holds the JState and the count of marked windows");
 
-}  // namespace
-
-// opts.partitions == 1: the single-table path. 0: as many partitions as lcb_junctions_plan finds for the budget. Otherwise that many.
-void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex& opts, const std::string& outFile,
-                              lcb_junction_stats_ex* stats)
+void needDevice(const char* fn, const char* cpuWay, int ordinal)
 {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        throw LcbError("no HIP device available: lcb_junctions_build runs only on the GPU (there is no CPU fallback; the CPU tool is lcb-mkgraph)");
+        throw LcbError(std::string("no HIP device available: ") + fn + " runs only on the GPU (there is no CPU fallback; " + cpuWay + ")");
     if (ordinal < 0 || ordinal >= count) throw LcbError("HIP device ordinal out of range");
-    lcb_junction_stats_ex X;
-    memset(&X, 0, sizeof(X));
+}
+
+// The input as the pipeline sees it: where the records lie in the code array, and the code bytes when the device has room for them.
+struct Source {
+    std::vector<uint64_t> base, recLen;      // base[r]: the code position of record r's first base; base[records] = len
+    uint64_t len = 1, nWindows = 0;
+    std::function<void(Run&)> upload;        // the records' codes -> R.dCodes (which holds a breaker everywhere), on or behind R.stream
+    void layout(int k)
+    {
+        base.resize(recLen.size() + 1);
+        len = 1; nWindows = 0;
+        for (size_t r = 0; r < recLen.size(); r++) {
+            base[r] = len;
+            len += recLen[r] + 1;
+            if (recLen[r] >= (uint64_t)k) nWindows += recLen[r] - k + 1;
+        }
+        base[recLen.size()] = len;
+    }
+};
+
+// Where a tile's records go: the junction file (lcb_junctions_build_impl) or the raw arrays of the graph build (lcb_graph_build_impl).
+struct Sink {
+    bool countFirst = false;                                              // begin() is told the number of junction windows of the whole input
+    std::function<void(uint64_t junctionWindows, uint32_t tileBuf)> begin;// the tables are complete, no tile has run
+    std::function<void(int64_t tile)> meanwhile;                          // on the host, while the device works on `tile`
+    std::function<void(int64_t tile, uint64_t n, uint64_t before)> tileDone;   // R.dOut holds the tile's n records; `before` = those of the tiles in front
+};
+
+// opts.partitions == 1: the single-table path. 0: as many partitions as lcb_junctions_plan finds for the budget. Otherwise that many.
+// Insert, classify, ids and emit; what becomes of a tile's records is the sink's. -> the junction k-mers (= the largest id).
+uint64_t junctionPipeline(Run& R, const Source& src, int k, int ordinal, const lcb_junction_opts_ex& opts, Sink& sink, lcb_junction_stats_ex& X, double& countMs)
+{
     lcb_junction_stats& S = X.base;
     const uint32_t tableLog2 = opts.table_log2;
     uint32_t P = opts.partitions;
-
-    // ---- read + encode (in place: the sequence strings become the code bytes)
-    double t = nowMs();
-    std::vector<lcb_fasta::Record> rec;
-    for (const std::string& f : fasta) {
-        try { lcb_fasta::readFasta(f, rec); } catch (std::exception& e) { throw LcbError(e.what()); }
-    }
-    std::vector<uint64_t> base(rec.size() + 1), recLen(rec.size());
-    uint64_t len = 1, nWindows = 0;
-    for (size_t r = 0; r < rec.size(); r++) {
-        base[r] = len;
-        recLen[r] = rec[r].seq.size();
-        len += recLen[r] + 1;
-        if (recLen[r] >= (size_t)k) nWindows += recLen[r] - k + 1;
-    }
-    base[rec.size()] = len;
-    for (lcb_fasta::Record& r : rec) {
-        char* p = &r.seq[0];
-        const int64_t n = (int64_t)r.seq.size();
-        #pragma omp parallel for schedule(static) if (n > (1 << 16))
-        for (int64_t i = 0; i < n; i++) { const int c = lcb_fasta::code(p[i]); p[i] = (char)(c < 0 ? 4 : c); }
-    }
-    S.records = (int64_t)rec.size();
+    const uint64_t len = src.len, nWindows = src.nWindows;
+    const std::string fn = R.fn;
+    S.records = (int64_t)src.recLen.size();
     S.windows = (int64_t)nWindows;
-    S.read_ms = nowMs() - t;
 
     // ---- plan: the budget, the number of partitions, and whether the first phase fits, before anything is allocated
-    Run R;
     HIP_CHECK(hipSetDevice(ordinal));
     size_t freeB = 0, totalB = 0;
     HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
@@ -218,7 +242,7 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     const uint32_t capLog2 = tableLog2 ? tableLog2 : lcb_junction_default_log2(nWindows, P);
     const uint64_t need = P == 1 ? len + tileBytes + LCB_JUNCTION_STATE_BYTES + lcb_junction_table_bytes(capLog2) : lcb_junction_phase_a_bytes(nWindows, len, tableLog2, P);
     if (need > R.budget)
-        throw LcbError("lcb_junctions_build: the input needs " + std::to_string(need) + " bytes of device memory with " + std::to_string(P) + " partition(s), " +
+        throw LcbError(fn + ": the input needs " + std::to_string(need) + " bytes of device memory with " + std::to_string(P) + " partition(s), " +
                        std::to_string(R.budget) + " may be used (sequence " + std::to_string(len) + " + 12 bytes per table slot + " +
                        (P == 1 ? "24 bytes per tile window)" : "one bit per base)"));
     X.partitions = P;
@@ -245,13 +269,11 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     HIP_CHECK(hipMemsetAsync(R.dCodes, 4, len, R.stream));
     HIP_CHECK(hipMemsetAsync(R.dState, 0, LCB_JUNCTION_STATE_BYTES, R.stream));
     HIP_CHECK(hipStreamSynchronize(R.stream));
-    for (size_t r = 0; r < rec.size(); r++)
-        if (!rec[r].seq.empty()) HIP_CHECK(hipMemcpy(R.dCodes + base[r], rec[r].seq.data(), rec[r].seq.size(), hipMemcpyHostToDevice));
+    src.upload(R);
     HIP_CHECK(hipEventRecord(R.evB, R.stream));
     HIP_CHECK(hipEventSynchronize(R.evB));
     HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
     S.upload_ms = ms;
-    std::vector<lcb_fasta::Record>().swap(rec);      // (the host copy of the sequence is no longer needed)
 
     // ---- table(s). One attempt to fill a fresh table of 2^log2 slots with `insert` (a launch on R.stream); false: too full, the
     // table is freed again.
@@ -276,7 +298,7 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     // A table that may take whatever it needs: too full -> twice the slots, from the start.
     auto growTable = [&](uint32_t log2, const std::string& name, const char* note, double& phaseMs, auto insert) {
         for (;; log2++) {
-            if (log2 > 40) throw LcbError("lcb_junctions_build: " + name + " would need more than 2^40 slots");
+            if (log2 > 40) throw LcbError(fn + ": " + name + " would need more than 2^40 slots");
             if (tryTable(log2, name + note, phaseMs, insert)) return;
         }
     };
@@ -288,6 +310,13 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
                   [&]() { junctionInsert<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, R.dState); });
         S.table_slots = (int64_t)(mask + 1);
         X.passes = 1;
+        if (sink.countFirst) {       // the sweep of a marking pass with the final masks, for the number alone
+            R.timed(countMs, [&]() {
+                lcb_graphk::graphCountWindows<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, dMarked, R.dState);
+            });
+            if (R.hState->lost) throw LcbError(fn + ": internal error: a k-mer of the input is missing from the table");
+            X.junction_windows = (int64_t) * (const unsigned long long*)((const char*)R.hState + sizeof(JState));
+        }
     } else {
         // ---- phase A: partition after partition, insert + mark. (M, r) = the k-mers with jPartition(kmer, M) == r. A table too full is
         // doubled; where the doubled table would not fit the budget, the partition is split instead: (M, r) = (2M, r) + (2M, r + M).
@@ -305,7 +334,7 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
             })) {
                 if (q.log2 < 40 && R.fits(lcb_junction_table_bytes(q.log2 + 1))) { q.log2++; continue; }
                 if (2 * q.M > (uint32_t)J_MAX_PARTS)
-                    throw LcbError("lcb_junctions_build: the k-mer table of partition " + std::to_string(q.r) + " of " + std::to_string(q.M) + " is too full at 2^" +
+                    throw LcbError(fn + ": the k-mer table of partition " + std::to_string(q.r) + " of " + std::to_string(q.M) + " is too full at 2^" +
                                    std::to_string(q.log2) + " slots, and twice the slots (" + std::to_string(lcb_junction_table_bytes(q.log2 + 1)) + " bytes on top of " +
                                    std::to_string(R.live) + " in use) do not fit the budget of " + std::to_string(R.budget));
                 todo.push_back(Part{2 * q.M, q.r + q.M, q.log2});
@@ -318,7 +347,7 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
             R.timed(X.mark_ms, [&]() {
                 junctionMarkPart<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dKey, R.dVal, mask, q.M, q.r, R.dBitmap, dMarked, R.dState);
             });
-            if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a k-mer of the input is missing from the table of its partition");
+            if (R.hState->lost) throw LcbError(fn + ": internal error: a k-mer of the input is missing from the table of its partition");
             R.release(R.dKey, (mask + 1) * sizeof(unsigned long long));
             R.release(R.dVal, (mask + 1) * sizeof(uint32_t));
             X.passes++;
@@ -329,17 +358,18 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
         allocTiles();
         growTable(lcb_junction_default_log2(nJ, 1), "the table of junction k-mers", " (phase B is not partitioned)", S.emit_ms,
                   [&]() { junctionFillMarked<<<gridAll, JT, 0, R.stream>>>(R.dCodes, len, k, R.dBitmap, R.dKey, R.dVal, mask, R.dState); });
-        if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a marked position holds no window");
+        if (R.hState->lost) throw LcbError(fn + ": internal error: a marked position holds no window");
         X.junction_table_slots = (int64_t)(mask + 1);
     }
 
-    // ---- tiles: classify + emit in file order; the host turns tile t - 1 into records while the device works on tile t
-    HIP_CHECK(hipHostMalloc((void**)&R.hOut[0], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc((void**)&R.hOut[1], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
-    R.part = outFile + ".part";
-    R.f = fopen(R.part.c_str(), "wb");
-    if (!R.f) { const std::string p = R.part; R.part.clear(); throw LcbError("cannot create " + p); }
-    Writer W{R, base, recLen, S.write_ms};
+    // ---- tiles: classify + emit in file order; the sink takes tile t - 1 while the device works on tile t
+    R.tableBytesKey = (mask + 1) * sizeof(unsigned long long);
+    R.tableBytesVal = (mask + 1) * sizeof(uint32_t);
+    R.tileBytes[0] = (uint64_t)tileBuf * sizeof(unsigned long long); R.tileBytes[1] = (uint64_t)tileBuf * sizeof(JRecord);
+    R.tileBytes[2] = R.tileBytes[3] = (uint64_t)nbMax * sizeof(uint32_t);
+    R.bitmapBytes = P == 1 ? 0 : bitmapWords * 8;
+    const bool counted = P > 1 || sink.countFirst;
+    sink.begin(counted ? (uint64_t)X.junction_windows : 0, tileBuf);
     uint64_t prevN = 0, ids = 0;
     int64_t tile = 0;
     for (uint64_t t0 = 0; t0 < len; t0 += tileWindows, tile++) {
@@ -352,19 +382,76 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
             junctionScan<<<1, 1024, 0, R.stream>>>(R.dCntJ, R.dCntF, nb, R.dState);
             junctionAssignIds<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntF, R.dState);
             junctionEmit<<<nb, JT, 0, R.stream>>>(R.dWslot, R.dVal, tileLen, R.dCntJ, t0, R.dOut);
-        }, [&]() { if (tile > 0) W.drain((int)((tile - 1) & 1), prevN); });
-        if (R.hState->lost) throw LcbError("lcb_junctions_build: internal error: a k-mer of the input is missing from the table");
+        }, [&]() { sink.meanwhile(tile); });
+        if (R.hState->lost) throw LcbError(fn + ": internal error: a k-mer of the input is missing from the table");
         prevN = R.hState->totJ;
         ids = R.hState->idNext;
-        if (ids > 0x7FFFFFFFull) throw LcbError("lcb_junctions_build: more than 2^31 - 1 junction k-mers (the value word holds 31 bits of id)");
-        if (prevN > tileLen) throw LcbError("lcb_junctions_build: internal error: more records than windows in a tile");
-        if (prevN) HIP_CHECK(hipMemcpyAsync(R.hOut[tile & 1], R.dOut, prevN * sizeof(JRecord), hipMemcpyDeviceToHost, R.stream));
-        HIP_CHECK(hipEventRecord(R.evCopy[tile & 1], R.stream));
+        if (ids > 0x7FFFFFFFull) throw LcbError(fn + ": more than 2^31 - 1 junction k-mers (the value word holds 31 bits of id)");
+        if (prevN > tileLen) throw LcbError(fn + ": internal error: more records than windows in a tile");
+        sink.tileDone(tile, prevN, (uint64_t)S.occurrences);
         S.occurrences += (int64_t)prevN;
     }
-    if (tile > 0) W.drain((int)((tile - 1) & 1), prevN);
-    if (P == 1) X.junction_windows = S.occurrences;
-    else if (S.occurrences != X.junction_windows) throw LcbError("lcb_junctions_build: internal error: the tiles found another number of junction windows than the passes marked");
+    sink.meanwhile(tile);
+    if (!counted) X.junction_windows = S.occurrences;
+    else if (S.occurrences != X.junction_windows) throw LcbError(fn + ": internal error: the tiles found another number of junction windows than the passes marked");
+    S.junction_kmers = (int64_t)ids;
+    S.tiles = tile;
+    return ids;
+}
+
+}  // namespace
+
+void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex& opts, const std::string& outFile,
+                              lcb_junction_stats_ex* stats)
+{
+    needDevice("lcb_junctions_build", "the CPU tool is lcb-mkgraph", ordinal);
+    lcb_junction_stats_ex X;
+    memset(&X, 0, sizeof(X));
+    lcb_junction_stats& S = X.base;
+
+    // ---- read + encode (in place: the sequence strings become the code bytes)
+    double t = nowMs();
+    std::vector<lcb_fasta::Record> rec;
+    for (const std::string& f : fasta) {
+        try { lcb_fasta::readFasta(f, rec); } catch (std::exception& e) { throw LcbError(e.what()); }
+    }
+    Source src;
+    for (const lcb_fasta::Record& r : rec) src.recLen.push_back(r.seq.size());
+    src.layout(k);
+    for (lcb_fasta::Record& r : rec) {
+        char* p = &r.seq[0];
+        const int64_t n = (int64_t)r.seq.size();
+        #pragma omp parallel for schedule(static) if (n > (1 << 16))
+        for (int64_t i = 0; i < n; i++) { const int c = lcb_fasta::code(p[i]); p[i] = (char)(c < 0 ? 4 : c); }
+    }
+    S.read_ms = nowMs() - t;
+    src.upload = [&](Run& R) {
+        for (size_t r = 0; r < rec.size(); r++)
+            if (!rec[r].seq.empty()) HIP_CHECK(hipMemcpy(R.dCodes + src.base[r], rec[r].seq.data(), rec[r].seq.size(), hipMemcpyHostToDevice));
+        std::vector<lcb_fasta::Record>().swap(rec);      // (the host copy of the sequence is no longer needed)
+    };
+
+    // ---- the file sink: the host turns tile t - 1 into records while the device works on tile t
+    Run R;
+    Writer W{R, src.base, src.recLen, S.write_ms};
+    uint64_t prevN = 0;
+    Sink sink;
+    sink.begin = [&](uint64_t, uint32_t tileBuf) {
+        HIP_CHECK(hipHostMalloc((void**)&R.hOut[0], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
+        HIP_CHECK(hipHostMalloc((void**)&R.hOut[1], (size_t)tileBuf * sizeof(JRecord), hipHostMallocDefault));
+        R.part = outFile + ".part";
+        R.f = fopen(R.part.c_str(), "wb");
+        if (!R.f) { const std::string p = R.part; R.part.clear(); throw LcbError("cannot create " + p); }
+    };
+    sink.meanwhile = [&](int64_t tile) { if (tile > 0) W.drain((int)((tile - 1) & 1), prevN); };
+    sink.tileDone = [&](int64_t tile, uint64_t n, uint64_t) {
+        prevN = n;
+        if (n) HIP_CHECK(hipMemcpyAsync(R.hOut[tile & 1], R.dOut, n * sizeof(JRecord), hipMemcpyDeviceToHost, R.stream));
+        HIP_CHECK(hipEventRecord(R.evCopy[tile & 1], R.stream));
+    };
+    double countMs = 0;
+    junctionPipeline(R, src, k, ordinal, opts, sink, X, countMs);
+    const std::vector<uint64_t>& recLen = src.recLen;
 
     // ---- finish: the separators of the sequences behind the last record, and the file under its name
     const double tw = nowMs();
@@ -376,8 +463,206 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
     if (rename(R.part.c_str(), outFile.c_str()) != 0) throw LcbError("cannot rename " + R.part + " to " + outFile);
     R.part.clear();
     S.write_ms += nowMs() - tw;
-    S.junction_kmers = (int64_t)ids;
-    S.tiles = tile;
     X.peak_device_bytes = R.peak;
     if (stats) *stats = X;
+}
+
+// ---- the graph from the FASTA files alone: the same pipeline with a sink that keeps a tile's records on the device,
+// then the kernels of lcb_graph_kernels.h. The host parses the FASTA (graph.cpp's parser: names, strings, validation), downloads the
+// kept arrays and builds the CSR (graph.cpp's code); it makes no pass over the raw records.
+lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
+                                lcb_graph_build_stats* stats)
+{
+    using namespace lcb_graphk;
+    const char* const FN = "lcb_graph_build";
+    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load", ordinal);
+    if (threads < 1) threads = 1;
+    lcb_graph_build_stats B;
+    memset(&B, 0, sizeof(B));
+    lcb_junction_stats_ex& X = B.junctions;
+
+    // ---- parse once, with the loader's parser; the strings stay in the graph
+    double t = nowMs();
+    std::unique_ptr<lcb_graph> g(new lcb_graph());
+    g->k = k;
+    const size_t nRec = lcb_graph_parse_fasta(*g, fasta, threads);
+    Source src;
+    for (size_t r = 0; r < nRec; r++) src.recLen.push_back(g->seq[r].size());
+    src.layout(k);
+    if (nRec > 0x7FFFFFFFull) throw LcbError(std::string(FN) + ": more than 2^31 - 1 FASTA records");
+    const std::vector<uint64_t>& base = src.base;
+    const uint64_t len = src.len;
+    B.parse_ms = nowMs() - t;
+
+    uint64_t N = 0, K = 0, ids = 0, patched = 0;
+    std::vector<unsigned long long> recFirst(nRec);
+    {
+        Run R;
+        R.fn = FN;
+        // the code bytes, made chunk by chunk in pinned memory (never in place: the strings are the graph's) and copied behind each other
+        src.upload = [&](Run& R) {
+            const double t0 = nowMs();
+            const uint64_t chunk = std::min<uint64_t>(len, 32ull << 20);
+            for (uint8_t*& p : R.hStage) HIP_CHECK(hipHostMalloc((void**)&p, chunk, hipHostMallocDefault));
+            size_t r = 0;
+            int64_t n = 0;
+            for (uint64_t c0 = 0; c0 < len; c0 += chunk, n++) {
+                const int slot = (int)(n & 1);
+                if (n >= 2) HIP_CHECK(hipEventSynchronize(R.evCopy[slot]));
+                uint8_t* s = R.hStage[slot];
+                const uint64_t c1 = std::min(len, c0 + chunk);
+                memset(s, 4, c1 - c0);
+                while (r < nRec && base[r] + src.recLen[r] <= c0) r++;
+                for (size_t q = r; q < nRec && base[q] < c1; q++) {
+                    const int64_t lo = (int64_t)std::max(base[q], c0), hi = (int64_t)std::min(base[q] + src.recLen[q], c1);
+                    const char* p = g->seq[q].data();
+                    const int64_t b = (int64_t)base[q], s0 = (int64_t)c0;
+                    #pragma omp parallel for num_threads(threads) schedule(static) if (hi - lo > (1 << 16))
+                    for (int64_t i = lo; i < hi; i++) { const int c = lcb_fasta::code(p[i - b]); s[i - s0] = (uint8_t)(c < 0 ? 4 : c); }
+                }
+                HIP_CHECK(hipMemcpyAsync(R.dCodes + c0, s, c1 - c0, hipMemcpyHostToDevice, R.stream));
+                HIP_CHECK(hipEventRecord(R.evCopy[slot], R.stream));
+            }
+            HIP_CHECK(hipStreamSynchronize(R.stream));
+            for (uint8_t*& p : R.hStage) { HIP_CHECK(hipHostFree(p)); p = nullptr; }
+            B.parse_ms += nowMs() - t0;
+        };
+        Sink sink;
+        sink.countFirst = true;
+        sink.begin = [&](uint64_t junctionWindows, uint32_t) {
+            N = junctionWindows;
+            R.alloc(R.dRawPos, std::max<uint64_t>(1, N) * sizeof(uint32_t), "the raw positions");
+            R.alloc(R.dRawId, std::max<uint64_t>(1, N) * sizeof(int32_t), "the raw ids");
+            R.alloc(R.dBase, (nRec + 1) * 8, "the record bases");
+            R.alloc(R.dRecFirst, (nRec + 1) * 8, "the first raw index of every record");
+            HIP_CHECK(hipMemcpyAsync(R.dBase, base.data(), (nRec + 1) * 8, hipMemcpyHostToDevice, R.stream));
+            HIP_CHECK(hipMemsetAsync(R.dRecFirst, 0xFF, (nRec + 1) * 8, R.stream));
+            HIP_CHECK(hipStreamSynchronize(R.stream));
+        };
+        sink.meanwhile = [](int64_t) {};
+        sink.tileDone = [&](int64_t, uint64_t n, uint64_t before) {
+            if (before + n > N) throw LcbError(std::string(FN) + ": internal error: the tiles hold more junction windows than the count found");
+            if (n) R.timed(B.take_ms, [&]() { graphTake<<<gridFor(n, G_T, FN), G_T, 0, R.stream>>>(R.dOut, (uint32_t)n, before, R.dBase, (uint32_t)nRec, R.dRawPos, R.dRawId, R.dRecFirst); });
+        };
+        ids = junctionPipeline(R, src, k, ordinal, opts, sink, X, B.count_ms);
+        X.base.read_ms = B.parse_ms;
+        B.raw_occurrences = (int64_t)N;
+
+        // ---- the junction finder's tables are done with
+        R.release(R.dKey, R.tableBytesKey);
+        R.release(R.dVal, R.tableBytesVal);
+        R.release(R.dBitmap, R.bitmapBytes);
+        R.release(R.dWslot, R.tileBytes[0]);
+        R.release(R.dOut, R.tileBytes[1]);
+        R.release(R.dCntJ, R.tileBytes[2]);
+        R.release(R.dCntF, R.tileBytes[3]);
+
+        // ---- what the loader refuses in a junction file: a chromosome without junctions in front of a later one; records behind the
+        // last chromosome (a junction file has no way to say that they exist)
+        double td = nowMs();
+        if (nRec) HIP_CHECK(hipMemcpy(recFirst.data(), R.dRecFirst, nRec * 8, hipMemcpyDeviceToHost));
+        B.download_bytes += nRec * 8;
+        size_t C = 0;
+        while (C < nRec && recFirst[C] != G_NONE) C++;
+        for (size_t r = C; r < nRec; r++)
+            if (recFirst[r] != G_NONE) throw LcbError("the junction file has a chromosome without junctions (unsupported)");
+        if (C < nRec) throw LcbError("the FASTA input has more records than the junction file has chromosomes");
+        for (size_t c = 0; c < C; c++)
+            if (recFirst[c] >= N || (c ? recFirst[c] <= recFirst[c - 1] : recFirst[c] != 0)) throw LcbError(std::string(FN) + ": internal error: the first raw indices of the records do not ascend");
+        B.download_ms += nowMs() - td;
+        g->nVertex = N ? (uint32_t)(ids + 1) : 0u;
+
+        // ---- abundance over the unfiltered records of both strands, keep-counts, their scan
+        const uint32_t nb = N ? gridFor(N, G_T, FN) : 0;
+        R.alloc(R.dCounter, ((uint64_t)g->nVertex + 1) * sizeof(uint32_t), "the abundance counters");
+        R.alloc(R.dBlockKept, ((uint64_t)nb + 1) * 8, "the keep-counts");
+        R.alloc(R.dTotals, 16, "the totals");
+        const char* aggEnv = getenv("LCB_GRAPH_ABUNDANCE");          // wave (aggregate equal ids within a wavefront) or plain; a measurement hook
+        const bool wave = aggEnv && std::string(aggEnv) == "wave";
+        R.timed(B.abundance_ms, [&]() {
+            HIP_CHECK(hipMemsetAsync(R.dCounter, 0, ((uint64_t)g->nVertex + 1) * sizeof(uint32_t), R.stream));
+            HIP_CHECK(hipMemsetAsync(R.dTotals, 0, 16, R.stream));
+            if (!N) return;
+            if (wave) graphAbundanceWave<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter);
+            else graphAbundance<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter);
+        });
+        unsigned long long totals[2] = {0, 0};
+        if (N) {
+            R.timed(B.compact_ms, [&]() {
+                graphKeepCount<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBlockKept);
+                graphScan<<<1, G_SCAN_T, 0, R.stream>>>(R.dBlockKept, nb, R.dTotals);
+            });
+            HIP_CHECK(hipMemcpy(totals, R.dTotals, 8, hipMemcpyDeviceToHost));
+            B.download_bytes += 8;
+        }
+        K = totals[0];
+        if (K > N) throw LcbError(std::string(FN) + ": internal error: more kept than raw occurrences");
+
+        // ---- compaction: the four per-position arrays and chrStart
+        R.alloc(R.dPosId, std::max<uint64_t>(1, K) * 4, "the kept ids");
+        R.alloc(R.dPosPos, std::max<uint64_t>(1, K) * 4, "the kept positions");
+        R.alloc(R.dPosCh, std::max<uint64_t>(1, K), "the characters");
+        R.alloc(R.dPosRevCh, std::max<uint64_t>(1, K), "the characters");
+        R.alloc(R.dChrStart, (C + 1) * 8, "chrStart");
+        if (N)
+            R.timed(B.compact_ms, [&]() {
+                graphCompact<<<nb, G_T, 0, R.stream>>>(R.dRawPos, R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBlockKept, R.dCodes, R.dBase, R.dRecFirst, (uint32_t)C, k,
+                                                       R.dPosId, R.dPosPos, R.dPosCh, R.dPosRevCh, R.dChrStart, R.dTotals + 1);
+            });
+
+        // ---- download: 10 bytes per kept occurrence, chrStart, the number of characters to patch
+        td = nowMs();
+        g->posId.resize(K); g->posPos.resize(K); g->posCh.resize(K); g->posRevCh.resize(K);
+        g->chrStart.assign(C + 1, 0);
+        if (K) {
+            HIP_CHECK(hipMemcpy(g->posId.data(), R.dPosId, K * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g->posPos.data(), R.dPosPos, K * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g->posCh.data(), R.dPosCh, K, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g->posRevCh.data(), R.dPosRevCh, K, hipMemcpyDeviceToHost));
+        }
+        if (C && N) HIP_CHECK(hipMemcpy(g->chrStart.data(), R.dChrStart, C * 8, hipMemcpyDeviceToHost));
+        g->chrStart[C] = K;
+        if (N) HIP_CHECK(hipMemcpy(&totals[1], R.dTotals + 1, 8, hipMemcpyDeviceToHost));
+        patched = totals[1];
+        B.download_bytes += 10 * K + 8 * C + 8;
+        B.download_ms += nowMs() - td;
+        B.peak_device_bytes = R.peak;
+        X.peak_device_bytes = R.peak;
+    }   // (the device is released here: everything below is the host's)
+
+    // ---- the per-chromosome limit, and the letters the code bytes do not have
+    const double tp = nowMs();
+    const size_t C = g->chrStart.size() - 1;
+    for (size_t c = 0; c < C; c++) {
+        if (g->chrStart[c + 1] < g->chrStart[c]) throw LcbError(std::string(FN) + ": internal error: chrStart does not ascend");
+        if (g->chrStart[c + 1] - g->chrStart[c] >= LCB_SEG_POSITIONS) throw LcbError("a chromosome with 2^32 - 2^20 or more junctions is not supported (the reference's own limit is 2^32 bp, hence fewer than 2^32 junctions, per chromosome)");
+    }
+    uint64_t found = 0;
+    #pragma omp parallel for num_threads(threads) schedule(dynamic, 1) reduction(+ : found)
+    for (int64_t c = 0; c < (int64_t)C; c++) {
+        const std::string& s = g->seq[(size_t)c];
+        uint8_t* const ch = g->posCh.data();
+        uint64_t i = g->chrStart[(size_t)c];
+        const uint64_t end = g->chrStart[(size_t)c + 1];
+        while (i < end) {
+            const uint8_t* hit = (const uint8_t*)memchr(ch + i, G_PATCH, end - i);
+            if (!hit) break;
+            i = (uint64_t)(hit - ch);
+            ch[i] = (uint8_t)s[(size_t)g->posPos[i] + (size_t)k];
+            found++;
+            i++;
+        }
+    }
+    if (found != patched) throw LcbError(std::string(FN) + ": internal error: the device marked " + std::to_string(patched) + " characters for the host, " + std::to_string(found) + " were found");
+    B.patched = (int64_t)patched;
+    B.download_ms += nowMs() - tp;
+
+    // ---- the host CSR, by the loader's code
+    t = nowMs();
+    lcb_graph_build_csr(g.get(), threads);
+    B.csr_ms = nowMs() - t;
+    B.kept_occurrences = (int64_t)K;
+    B.vertices = (int64_t)g->nVertex;
+    if (stats) *stats = B;
+    return g.release();
 }

@@ -38,6 +38,13 @@ void lcb_set_error(const std::string& msg);
 
 // graph.cpp
 lcb_graph* lcb_graph_load_impl(const char* junctionFile, const std::vector<std::string>& fasta, int k, int abundance, int threads);
+// ... its FASTA parser alone: chrName and seq of every record of the files, validated as lcb_graph_load validates them; -> the records
+size_t lcb_graph_parse_fasta(lcb_graph& g, const std::vector<std::string>& fasta, int threads);
+// ... and its last step: occStart / occG / occChr from nVertex, chrStart and posId
+void lcb_graph_build_csr(lcb_graph* g, int threads);
+// junctions.hip — the graph from the FASTA files alone, on one MI355X; arguments are already validated
+lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
+                                lcb_graph_build_stats* stats);
 // junctions.hip — GPU junction finder (byte-identical to tools/mkgraph.cpp); arguments are already validated
 void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int ordinal, const lcb_junction_opts_ex& opts, const std::string& outFile,
                               lcb_junction_stats_ex* stats);

@@ -5,8 +5,9 @@
 //   sibeliaz-lcb --graph <junctions> <fasta...> -k <odd> -b <int> -o <dir> -m <int> -t <int> --abundance <int> [--noseq] --chunks <int>
 // `-t` stays "host threads" (loading, seed enumeration); the GPU is chosen by the environment
 // (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag, and so are the place where the seeds are
-// enumerated (LCB_SEEDS=host, the default, or device) and the place where the device's tables are computed (LCB_TABLES=host, the
-// default, or device).
+// enumerated (LCB_SEEDS=host, the default, or device), the place where the device's tables are computed (LCB_TABLES=host, the
+// default, or device) and the way to the graph (LCB_JUNCTIONS=file, the default: the junction file of --graph; or device: the
+// junctions come from the FASTA arguments on the GPU, --graph is still required by the parser but never opened).
 // The block finder itself runs on the MI355X through the C ABI in include/lcb.h.
 #include <cstdio>
 #include <cstdlib>
@@ -124,6 +125,14 @@ int main(int argc, char** argv)
         return 1;
     }
     const bool deviceTables = tableRoute == "device";
+    // ... and the way to the graph (LCB_JUNCTIONS=file, the default, or device)
+    const char* junctionsEnv = getenv("LCB_JUNCTIONS");
+    const std::string junctionRoute = junctionsEnv && *junctionsEnv ? junctionsEnv : "file";
+    if (junctionRoute != "file" && junctionRoute != "device") {
+        std::cerr << "error: LCB_JUNCTIONS is '" << junctionRoute << "': it is file (the default) or device" << std::endl;
+        return 1;
+    }
+    const bool deviceJunctions = junctionRoute == "device";
     {
         const char* gpus = getenv("LCB_GPUS");
         if (deviceTables && gpus && *gpus && atoi(gpus) > 1) {
@@ -142,7 +151,21 @@ int main(int argc, char** argv)
         std::cout << "Loading the graph..." << std::endl;                                      // sibeliaz.cpp:124
         std::vector<const char*> fa;
         for (auto& f : a.fasta) fa.push_back(f.c_str());
-        g = lcb_graph_load(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t);
+        if (deviceJunctions) {
+            // on LCB_DEVICE (device 0 of an LCB_GPUS=N set); the graph is a host object and the build has released the device when it returns
+            const char* ordEnv = getenv("LCB_DEVICE");
+            const char* setEnv = getenv("LCB_GPUS");
+            const bool several = setEnv && *setEnv && atoi(setEnv) > 1;
+            lcb_graph_build_stats gs;
+            g = lcb_graph_build(fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t, !several && ordEnv && *ordEnv ? atoi(ordEnv) : 0, nullptr, &gs);
+            if (g && getenv("LCB_VERBOSE"))
+                std::cerr << "lcb: graph=device records=" << gs.junctions.base.records << " raw=" << gs.raw_occurrences << " kept=" << gs.kept_occurrences << " vertices=" << gs.vertices
+                          << " patched=" << gs.patched << " partitions=" << gs.junctions.partitions << " download_bytes=" << gs.download_bytes << " peak_device_bytes="
+                          << gs.peak_device_bytes << " parse_ms=" << gs.parse_ms << " upload_ms=" << gs.junctions.base.upload_ms << " insert_ms=" << gs.junctions.base.insert_ms
+                          << " mark_ms=" << gs.junctions.mark_ms << " count_ms=" << gs.count_ms << " emit_ms=" << gs.junctions.base.emit_ms << " take_ms=" << gs.take_ms
+                          << " abundance_ms=" << gs.abundance_ms << " compact_ms=" << gs.compact_ms << " download_ms=" << gs.download_ms << " csr_ms=" << gs.csr_ms << std::endl;
+        } else
+            g = lcb_graph_load(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t);
         if (!g) { fail(); break; }
         std::cout << "Analyzing the graph..." << std::endl;                                    // sibeliaz.cpp:132
         lcb_params p;
