@@ -331,6 +331,32 @@ lcb_device* lcb_device_create_tables(const lcb_graph* g, const lcb_params* p, in
 #define LCB_TABLE_SEG_BASE 8     /* uint64_t [32] */
 int lcb_device_table_read(lcb_device* d, int table, uint64_t first, uint64_t n, void* out, uint64_t out_bytes);
 
+/* ---- one call from the FASTA files to a graph and a device ready for lcb_find_blocks: lcb_graph_build and
+ * lcb_device_create_tables(.., LCB_TABLES_DEVICE, ..) in one, with the graph handed over in HBM. The junction finder, the abundance
+ * filter and the compaction run as in lcb_graph_build; the four per-position arrays they leave on the device BECOME the device's
+ * tables (adopted without a copy; copied segment by segment, device to device, only under the seg_gap test hook) and are downloaded
+ * once, 10 bytes per kept occurrence, for the host's copy. The table build of LCB_TABLES_DEVICE then runs on them, and the host CSR
+ * (occStart / occG / occChr) is taken from its scan and its sort instead of being computed on host threads: nothing crosses the bus
+ * twice, no table is computed twice. The letters the code bytes do not have are patched in both copies (the host finds them, a kernel
+ * writes the device's).
+ * *graph and *device are exactly what lcb_graph_build followed by lcb_device_create_tables(g, p, ordinal, dopts, LCB_TABLES_DEVICE, ..)
+ * return - the same graph, the same bytes in all nine tables of lcb_device_table_read, the same options decided - and never depend on
+ * jopts. Every call that takes a graph or a device takes them; the caller destroys the device before it frees the graph. One GPU
+ * only (as LCB_TABLES_DEVICE), and no CPU fallback: without a GPU this fails. LCB_ERR on error (lcb_last_error): both out pointers
+ * are NULL then, and no device memory, pinned memory or file is left behind. */
+typedef struct {            /* output only; may be NULL */
+    lcb_graph_build_stats graph;    /* as lcb_graph_build reports it; csr_ms = 0 (no host CSR is computed), download_bytes as counted here */
+    lcb_table_stats tables;         /* as lcb_device_create_tables reports it; upload_bytes = the segment plan and the patch list only */
+    double place_ms;                /* device: the arrays to their places in the device tables (0 when they are adopted) */
+    double patch_ms;                /* device: the patch list up and handPatch */
+    double csr_download_ms;         /* handOccChr (device) + the copies of occStart, the sorted payloads and occChr + their widening (host wall time) */
+    uint64_t csr_download_bytes;    /* (sizeof(Q) + 4) per kept occurrence + sizeof(Q) per vertex + 1, Q = 4 bytes, 8 with several segments or a seg_cap */
+    uint64_t peak_device_bytes;     /* most device memory held at one time, by the route's own account (junction part and tables) */
+} lcb_open_stats;
+int lcb_open_fasta(const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, const lcb_params* p, int device_ordinal,
+                   const lcb_junction_opts_ex* jopts /* may be NULL */, const lcb_device_opts* dopts /* may be NULL */,
+                   lcb_graph** graph, lcb_device** device, lcb_open_stats* stats /* may be NULL */);
+
 /* THE HOT PATH: ProcessVertex::Process (blocksfinder.h:228-310) for a batch of seeds, each against the
  * device's current `used` state, one seed per workgroup (wavefront 0 runs the seed, the others share its look-ahead votes). offsets has n+1 entries; the instances of seed
  * i are inst[offsets[i] .. offsets[i+1]). Returns LCB_OK, or LCB_ERR (e.g. inst_cap too small: the needed

@@ -125,6 +125,12 @@ class TableStats(C.Structure):
                 ("upload_bytes", C.c_uint64), ("device_bytes", C.c_uint64)] + [(n, C.c_double) for n in ("upload_ms", "window_ms", "csr_ms", "sort_ms", "gather_ms")]
 
 
+class OpenStats(C.Structure):
+    """lcb_open_stats: what lcb_open_fasta reports."""
+    _fields_ = [("graph", GraphBuildStats), ("tables", TableStats)] + [(n, C.c_double) for n in ("place_ms", "patch_ms", "csr_download_ms")] + [
+        ("csr_download_bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64)]
+
+
 TABLE_ROUTES = {"host": 0, "device": 1}      # LCB_TABLES_HOST / LCB_TABLES_DEVICE
 # lcb_device_table_read: name -> (LCB_TABLE_* id, dtype of an element)
 OCC_REC_DTYPE = np.dtype([("g", "<u4"), ("cw", "<u4"), ("pos", "<u4"), ("id", "<i4")])
@@ -152,7 +158,7 @@ EXPORTS = [
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
     "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan", "lcb_device_enumerate_seeds", "lcb_device_sort_seeds", "lcb_gpus_device",
-    "lcb_device_create_tables", "lcb_device_table_read", "lcb_graph_build",
+    "lcb_device_create_tables", "lcb_device_table_read", "lcb_graph_build", "lcb_open_fasta",
 ]
 
 
@@ -174,6 +180,8 @@ def load_library():
     L.lcb_graph_free.argtypes = [vp]
     L.lcb_graph_build.restype = vp
     L.lcb_graph_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JunctionOptsEx), C.POINTER(GraphBuildStats)]
+    L.lcb_open_fasta.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.POINTER(JunctionOptsEx), C.POINTER(DeviceOpts),
+                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(OpenStats)]
     for f in ("lcb_graph_n_chr", "lcb_graph_n_pos", "lcb_graph_n_vertices"):
         getattr(L, f).restype = i64
         getattr(L, f).argtypes = [vp]
@@ -534,6 +542,44 @@ class Device:
         ms, n = C.c_double(), C.c_int64()
         self.L.lcb_device_kernel_time(self.h, C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+def open_fasta(fasta_files, k, params, abundance=150, threads=1, device=0, partitions=None, mem_budget=None, stats=False, device_opts=None, **junction_opts):
+    """FASTA files -> (JunctionStorage, Device) in one call on one MI355X (lcb_open_fasta): what JunctionStorage.build followed by
+    Device(storage, params, device, tables="device", **device_opts) gives - the same storage, the same bytes in every table of the device -
+    with the graph handed over in HBM: the arrays the graph build leaves on the GPU become the device's tables, the host CSR comes from
+    the table build. junction_opts (table_log2, tile_windows), partitions and mem_budget as in JunctionStorage.build; device_opts: a dict
+    of lcb_device_opts fields. Close the device before the storage. stats=True: -> (storage, device, lcb_open_stats as a dict: the graph
+    part flattened as JunctionStorage.build flattens it - csr_ms is the host CSR's, 0 here -, the table part under its own names with
+    "table_" in front where a name would repeat: table_vertices, table_upload_ms, table_csr_ms). One GPU, no CPU fallback."""
+    o = _junction_opts(JunctionOptsEx, dict(junction_opts, partitions=1 if partitions is None else partitions, mem_budget=mem_budget or 0),
+                       ("abi", "table_log2", "tile_windows", "partitions", "mem_budget"))
+    do = DeviceOpts()
+    for name, v in (device_opts or {}).items():
+        if not hasattr(do, name):
+            raise TypeError("unknown device option %r" % name)
+        setattr(do, name, int(v))
+    if isinstance(fasta_files, (str, bytes, os.PathLike)):
+        fasta_files = [fasta_files]
+    files = [os.fsencode(f) for f in fasta_files]
+    arr = (C.c_char_p * max(1, len(files)))(*files)
+    L = load_library()
+    g, d, st = C.c_void_p(), C.c_void_p(), OpenStats()
+    if L.lcb_open_fasta(arr, len(files), int(k), int(abundance), int(threads), C.byref(params), int(device), C.byref(o), C.byref(do), C.byref(g), C.byref(d), C.byref(st)):
+        raise _err(L)
+    storage = JunctionStorage.__new__(JunctionStorage)
+    storage.L, storage.k, storage.h = L, k, g.value
+    dev = Device.__new__(Device)
+    dev.L, dev.storage, dev.params, dev.h, dev.tables = L, storage, params, d.value, "device"
+    dev.table_stats = {f: getattr(st.tables, f) for f, _ in TableStats._fields_}
+    if not stats:
+        return storage, dev
+    out = {f: getattr(st.graph.junctions.base, f) for f, _ in JunctionStats._fields_}
+    out.update({f: getattr(st.graph.junctions, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
+    out.update({f: getattr(st.graph, f) for f, _ in GraphBuildStats._fields_ if f != "junctions"})
+    out.update({("table_" + f if f in out else f): getattr(st.tables, f) for f, _ in TableStats._fields_})
+    out.update({f: getattr(st, f) for f, _ in OpenStats._fields_ if f not in ("graph", "tables")})
+    return storage, dev, out
 
 
 class Comm:

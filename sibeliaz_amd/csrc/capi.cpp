@@ -159,6 +159,35 @@ lcb_graph* lcb_graph_build(const char* const* fasta_files, int n_fasta, int k, i
     LCB_CATCH(nullptr)
 }
 
+int lcb_open_fasta(const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, const lcb_params* p, int device_ordinal,
+                   const lcb_junction_opts_ex* jopts, const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats)
+{
+    if (graph) *graph = nullptr;
+    if (device) *device = nullptr;
+    LCB_TRY
+    const std::string fn = "lcb_open_fasta";
+    if (!graph || !device || !p) throw LcbError(fn + ": null argument");
+    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
+    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(fn + ": k must be odd and in 3..31, not " + std::to_string(k));
+    checkJunctionOpts(jopts, "lcb_junction_opts_ex");
+    checkAbi(nullptr, dopts);
+    if (p->max_branch >= 65000 || p->looking_depth >= 65000) throw LcbError("maxBranchSize / lookingDepth of 65000 or more are not supported by the device vote table");
+    std::vector<std::string> fa;
+    for (int i = 0; i < n_fasta; i++) {
+        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
+        FILE* f = fopen(fasta_files[i], "rb");         // (what the parser would say, said before a device is looked for)
+        if (!f) throw LcbError(std::string("Can't open file ") + fasta_files[i]);
+        fclose(f);
+        fa.push_back(fasta_files[i]);
+    }
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    lcb_open_fasta_impl(fa, k, abundance, threads, p, device_ordinal, jopts ? *jopts : o, dopts, graph, device, stats);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
+
 int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget, int32_t* partitions, uint64_t* need_bytes)
 {
     LCB_TRY

@@ -499,8 +499,9 @@ struct lcb_device_impl {
 // diagnostics, lanes. Whatever a step makes is registered in d->own as it is made, so a failure anywhere leaves nothing behind.
 namespace {
 
-// option defaults and checks
-void createOptions(lcb_device_impl* d, uint32_t nCu)
+// option defaults and checks, in two parts: what the tables need (the segment plan), and what follows from the graph's occurrence lists
+// (the pools of the compact variant, the slot counts). The hand-over route makes the tables in between: its lists exist only then.
+void createPlan(lcb_device_impl* d)
 {
     const lcb_graph* g = d->g;
     lcb_device_opts& o = d->o;
@@ -512,6 +513,12 @@ void createOptions(lcb_device_impl* d, uint32_t nCu)
     // the compact variant's pools: small ones where a vertex has few occurrences (paths of few instances: k = 25 inputs of 8-16 genomes, 6-12
     // occurrences per vertex; the 62-strain shape has 26 at 1/40 of its size and more at full size, and its paths outgrow 128 instances)
     if (o.compact_pools > 2) throw LcbError("lcb_device_opts.compact_pools: 0 (by the input), 1 (256 instances / 1 024 vote slots) or 2 (128 / 512)");
+}
+
+void createPools(lcb_device_impl* d, uint32_t nCu)
+{
+    const lcb_graph* g = d->g;
+    lcb_device_opts& o = d->o;
     d->compactAuto = o.compact_pools == 0;
     // (the occurrence-weighted mean of the occurrences per vertex: "the typical occurrence belongs to a vertex with that many" - 6-14 for the k = 25 shapes of 8 / 16
     // genomes, 35+ for the 62-strain shape, 25 for the 10-strain one, whose many strain-private vertices would hide that in a plain mean)
@@ -532,6 +539,12 @@ void createOptions(lcb_device_impl* d, uint32_t nCu)
     if (!o.wide_threshold) o.wide_threshold = 2 * o.wide_slots;
     if (!o.screen_min) o.screen_min = 2048;
     if (o.path_cap & (o.path_cap - 1)) throw LcbError("lcb_device_opts.path_cap must be a power of two");
+}
+
+void createOptions(lcb_device_impl* d, uint32_t nCu)
+{
+    createPlan(d);
+    createPools(d, nCu);
 }
 
 // The device route of the tables (LCB_TABLES_DEVICE; tables.hip): only the four per-position arrays go up; posWin,
@@ -559,6 +572,106 @@ void createTablesOnDevice(lcb_device_impl* d)
     job.drop = [](void* o, void* p) { uint8_t* q = (uint8_t*)p; ((lcb_device_impl*)o)->drop(q); };
     lcb_build_tables_impl(job, d->tableStats);
     d->T.occRec = (const uint4*)job.occRec;
+}
+
+// The tables on the hand-over route (lcb_open_fasta): the four per-position arrays are already in HBM, left there by the
+// graph build. They become the device's tables - adopted as they are where the device index of host position q is q (no seg_gap:
+// every production run), copied segment by segment, device to device, under the seg_gap test hook - and are downloaded once for the
+// graph's vectors. The letters the code bytes do not have are found in the downloaded posCh and patched in both copies. Then the table
+// build of createTablesOnDevice runs, and the graph's CSR is taken from it (LcbTableHandover). `g` is complete on return.
+void createTablesHandover(lcb_device_impl* d, lcb_graph* g, LcbHandover& ho)
+{
+    const char* fn = ho.fn;
+    lcb_open_stats& S = *ho.stats;
+    LcbKeptArrays& kept = ho.kept;
+    const LcbSegPlan& plan = d->plan;
+    const uint64_t K = g->nPos(), D = plan.devPositions ? plan.devPositions : 1, V1 = (uint64_t)g->nVertex + 1, qBytes = d->seg ? 8 : 4;
+    if (kept.K != K) throw LcbError(std::string(fn) + ": internal error: the holder has " + std::to_string(kept.K) + " positions, the graph " + std::to_string(K));
+    {
+        std::vector<uint2> lh(g->nChr());
+        for (size_t c = 0; c < lh.size(); c++) lh[c] = uint2{plan.chrLo[c], plan.chrHi[c]};
+        d->T.chrLoHi = d->upload(lh.data(), lh.size());
+        d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
+    }
+    const uint64_t small = (uint64_t)g->nChr() * 8 + plan.segDev.size() * 8, dense = 10 * std::max<uint64_t>(1, K);
+    int32_t* posId = nullptr;
+    uint32_t* posPos = nullptr;
+    uint8_t *posCh = nullptr, *posRevCh = nullptr;
+    uint64_t placePeak = small + dense;
+    // ---- place
+    if (!plan.gap) {
+        // the device's owner takes each array in the step that takes it out of the holder
+        lcb_tables_need_impl(fn, D * 4 + V1 * qBytes, "the look-ahead windows of " + std::to_string(K) + " positions (4 bytes each) and the lists of " + std::to_string(g->nVertex) + " vertices");
+        posId = (int32_t*)d->own.make(LCB_OWN_DEVICE, [&] { return (void*)LcbKeptArrays::take(kept.posId); });
+        posPos = (uint32_t*)d->own.make(LCB_OWN_DEVICE, [&] { return (void*)LcbKeptArrays::take(kept.posPos); });
+        posCh = (uint8_t*)d->own.make(LCB_OWN_DEVICE, [&] { return (void*)LcbKeptArrays::take(kept.posCh); });
+        posRevCh = (uint8_t*)d->own.make(LCB_OWN_DEVICE, [&] { return (void*)LcbKeptArrays::take(kept.posRevCh); });
+    } else {
+        lcb_tables_need_impl(fn, D * 14 + V1 * qBytes, "the per-position tables of " + std::to_string(K) + " positions (14 bytes each) and the lists of " + std::to_string(g->nVertex) + " vertices");
+        posId = d->devAlloc<int32_t>((size_t)D * 4);
+        posPos = d->devAlloc<uint32_t>((size_t)D * 4);
+        posCh = d->devAlloc<uint8_t>((size_t)D);
+        posRevCh = d->devAlloc<uint8_t>((size_t)D);
+        placePeak += 10 * D;
+        hipEvent_t e0 = d->newEvent(), e1 = d->newEvent();
+        HIP_CHECK(hipEventRecord(e0, d->stream));
+        for (uint32_t sg = 0; sg < plan.nSeg(); sg++) {        // (the gaps are neither read nor written)
+            const uint64_t a = plan.segStart[sg], n = plan.segStart[sg + 1] - a, at = plan.segDev[sg];
+            if (!n) continue;
+            HIP_CHECK(hipMemcpyAsync(posId + at, kept.posId + a, (size_t)n * 4, hipMemcpyDeviceToDevice, d->stream));
+            HIP_CHECK(hipMemcpyAsync(posPos + at, kept.posPos + a, (size_t)n * 4, hipMemcpyDeviceToDevice, d->stream));
+            HIP_CHECK(hipMemcpyAsync(posCh + at, kept.posCh + a, (size_t)n, hipMemcpyDeviceToDevice, d->stream));
+            HIP_CHECK(hipMemcpyAsync(posRevCh + at, kept.posRevCh + a, (size_t)n, hipMemcpyDeviceToDevice, d->stream));
+        }
+        HIP_CHECK(hipEventRecord(e1, d->stream));
+        HIP_CHECK(hipStreamSynchronize(d->stream));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        S.place_ms = ms;
+        HIP_CHECK((hipError_t)d->own.drop(e0));
+        HIP_CHECK((hipError_t)d->own.drop(e1));
+        kept.reset();                                          // the dense copies lived until the last segment copy
+    }
+    d->T.posId = posId; d->T.posPos = posPos; d->T.posCh = posCh; d->T.posRevCh = posRevCh;
+    const uint64_t resident = small + (plan.gap ? 10 * D : dense);
+
+    // ---- the one download: 10 bytes per kept occurrence, from the device's own tables
+    double t0 = nowMs();
+    for (uint32_t sg = 0; sg < plan.nSeg(); sg++) {
+        const uint64_t a = plan.segStart[sg], n = plan.segStart[sg + 1] - a, at = plan.segDev[sg];
+        if (!n) continue;
+        HIP_CHECK(hipMemcpy(g->posId.data() + a, posId + at, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(g->posPos.data() + a, posPos + at, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(g->posCh.data() + a, posCh + at, (size_t)n, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(g->posRevCh.data() + a, posRevCh + at, (size_t)n, hipMemcpyDeviceToHost));
+    }
+    S.graph.download_bytes += 10 * K;
+
+    // ---- the letters the code bytes do not have: the host's copy now, the device's inside the table build
+    std::vector<uint64_t> patchQ;
+    std::vector<uint8_t> patchLetter;
+    const uint64_t found = lcb_graph_patch_chars(g, ho.threads, &patchQ, &patchLetter);
+    if (found != ho.patched) throw LcbError(std::string(fn) + ": internal error: the device marked " + std::to_string(ho.patched) + " characters for the host, " + std::to_string(found) + " were found");
+    S.graph.patched = (int64_t)found;
+    S.graph.download_ms += nowMs() - t0;
+
+    // ---- the table build, with the CSR taken from it
+    uint32_t* win = d->devAlloc<uint32_t>((size_t)D * sizeof(uint32_t));
+    d->T.posWin = win;
+    LcbTableHandover hand;
+    hand.g = g; hand.posCh = posCh; hand.patchQ = patchQ.data(); hand.patchLetter = patchLetter.data(); hand.nPatch = (uint64_t)patchQ.size();
+    LcbTableJob job;
+    job.fn = fn; job.stream = (void*)d->stream; job.g = g; job.plan = &plan; job.seg = d->seg; job.maxBranch = (uint32_t)d->p.max_branch;
+    job.posId = posId; job.posPos = posPos; job.segBase = d->T.segBase; job.posWin = win; job.hand = &hand;
+    if (d->seg) { uint64_t* os = d->devAlloc<uint64_t>((size_t)V1 * 8); d->T.occStart64 = os; d->T.occStart32 = nullptr; job.occStart = os; }
+    else { uint32_t* os = d->devAlloc<uint32_t>((size_t)V1 * 4); d->T.occStart32 = os; d->T.occStart64 = nullptr; job.occStart = os; }
+    job.owner = d;
+    job.alloc = [](void* o, size_t bytes) { return (void*)((lcb_device_impl*)o)->devAlloc<uint8_t>(bytes); };
+    job.drop = [](void* o, void* p) { uint8_t* q = (uint8_t*)p; ((lcb_device_impl*)o)->drop(q); };
+    lcb_build_tables_impl(job, d->tableStats);
+    d->T.occRec = (const uint4*)job.occRec;
+    S.patch_ms = hand.patchMs; S.csr_download_ms = hand.csrMs; S.csr_download_bytes = hand.csrBytes;
+    S.peak_device_bytes = std::max(std::max(ho.junctionPeak, placePeak), resident + D * 4 + V1 * qBytes + hand.peakBytes);
 }
 
 // the read-only tables (file header)
@@ -721,10 +834,9 @@ void createLanes(lcb_device_impl* d, uint32_t nLanes, uint32_t nCu, int prioLow)
 
 lcb_device* lcb_device_create_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts) { return lcb_device_create_tables_impl(g, p, ordinal, opts, LCB_TABLES_HOST, nullptr); }
 
-lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats)
+// ho: the hand-over route (g is then `gw`, which the table step completes); null: the graph is complete and read only
+static lcb_device* createDevice(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats, lcb_graph* gw, LcbHandover* ho)
 {
-    if (tables != LCB_TABLES_HOST && tables != LCB_TABLES_DEVICE)
-        throw LcbError("lcb_device_create_tables: tables is " + std::to_string(tables) + ": LCB_TABLES_HOST (0) or LCB_TABLES_DEVICE (1)");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         throw LcbError("no HIP device available: the block-finder hot path runs only on the GPU (there is no CPU fallback)");
@@ -739,7 +851,8 @@ lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* 
         hipDeviceProp_t prop;
         HIP_CHECK(hipGetDeviceProperties(&prop, ordinal));
         const uint32_t nCu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
-        createOptions(d, nCu);
+        if (ho) createPlan(d);
+        else createOptions(d, nCu);
         // needed results ahead of speculation: the stream of the synchronous launches gets the highest HIP stream priority, the side
         // lanes' streams the lowest (numerically lower = higher priority; -4 % per pass together with the early critical launch,
         // profiles/r04/ab_first.txt)
@@ -748,7 +861,11 @@ lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* 
         d->stream = d->newStream(&prioHigh);
         for (hipEvent_t* e : {&d->bufs.e0, &d->bufs.e1, &d->bufsEarly.e0, &d->bufsEarly.e1}) *e = d->newEvent();
         const uint32_t nLanes = d->o.side_lanes == 0xFFFFFFFFu ? 0u : (d->o.side_lanes ? d->o.side_lanes : 4u);
-        createTables(d);
+        if (ho) {
+            createTablesHandover(d, gw, *ho);
+            createPools(d, nCu);              // (from the lists the table step has just given the graph)
+        } else
+            createTables(d);
         d->tableStats.positions = (int64_t)g->nPos(); d->tableStats.vertices = g->nVertex;
         if (stats) *stats = d->tableStats;
         createUsed(d, nLanes);
@@ -763,6 +880,20 @@ lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* 
         throw;
     }
     return handle;
+}
+
+lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats)
+{
+    if (tables != LCB_TABLES_HOST && tables != LCB_TABLES_DEVICE)
+        throw LcbError("lcb_device_create_tables: tables is " + std::to_string(tables) + ": LCB_TABLES_HOST (0) or LCB_TABLES_DEVICE (1)");
+    return createDevice(g, p, ordinal, opts, tables, stats, nullptr, nullptr);
+}
+
+lcb_device* lcb_device_create_handover_impl(lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, LcbHandover& ho)
+{
+    // (a device that fails half-made releases what it has taken; what it has not taken yet is still the holder's, and goes here)
+    struct Emptied { LcbKeptArrays& k; ~Emptied() { k.reset(); } } emptied{ho.kept};
+    return createDevice(g, p, ordinal, opts, LCB_TABLES_DEVICE, &ho.stats->tables, g, &ho);
 }
 
 static void lcb_device_drop_async(lcb_device_impl* d);

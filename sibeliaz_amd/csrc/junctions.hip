@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "lcb_device.h"
 #include "lcb_fasta.h"
 #include "lcb_graph_kernels.h"
 #include "lcb_host.h"
@@ -470,20 +471,22 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
 // ---- the graph from the FASTA files alone: the same pipeline with a sink that keeps a tile's records on the device,
 // then the kernels of lcb_graph_kernels.h. The host parses the FASTA (graph.cpp's parser: names, strings, validation), downloads the
 // kept arrays and builds the CSR (graph.cpp's code); it makes no pass over the raw records.
-lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
-                                lcb_graph_build_stats* stats)
+//
+// The device part is shared by its two callers (graphOnDevice): lcb_graph_build_impl downloads the kept arrays and releases the device,
+// lcb_open_fasta_impl passes them on to the device that is being created.
+namespace {
+
+// Parse, junction pipeline, abundance filter, compaction: on return R holds the four kept arrays (K positions each) besides what is
+// left of the run, g has its names, sequences, nVertex and chrStart, and its per-position vectors have their size (nothing in them
+// yet). The per-chromosome limit is checked. -> the characters the compaction marked for the host (the sentinel in posCh).
+uint64_t graphOnDevice(Run& R, const char* const FN, lcb_graph* g, const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal,
+                       const lcb_junction_opts_ex& opts, lcb_graph_build_stats& B, uint64_t& K)
 {
     using namespace lcb_graphk;
-    const char* const FN = "lcb_graph_build";
-    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load", ordinal);
-    if (threads < 1) threads = 1;
-    lcb_graph_build_stats B;
-    memset(&B, 0, sizeof(B));
     lcb_junction_stats_ex& X = B.junctions;
 
     // ---- parse once, with the loader's parser; the strings stay in the graph
     double t = nowMs();
-    std::unique_ptr<lcb_graph> g(new lcb_graph());
     g->k = k;
     const size_t nRec = lcb_graph_parse_fasta(*g, fasta, threads);
     Source src;
@@ -494,10 +497,9 @@ lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, in
     const uint64_t len = src.len;
     B.parse_ms = nowMs() - t;
 
-    uint64_t N = 0, K = 0, ids = 0, patched = 0;
+    uint64_t N = 0, ids = 0;
     std::vector<unsigned long long> recFirst(nRec);
     {
-        Run R;
         R.fn = FN;
         // the code bytes, made chunk by chunk in pinned memory (never in place: the strings are the graph's) and copied behind each other
         src.upload = [&](Run& R) {
@@ -610,33 +612,32 @@ lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, in
                                                        R.dPosId, R.dPosPos, R.dPosCh, R.dPosRevCh, R.dChrStart, R.dTotals + 1);
             });
 
-        // ---- download: 10 bytes per kept occurrence, chrStart, the number of characters to patch
+        // ---- download: chrStart, the number of characters to patch (both tiny); the per-chromosome limit
         td = nowMs();
         g->posId.resize(K); g->posPos.resize(K); g->posCh.resize(K); g->posRevCh.resize(K);
         g->chrStart.assign(C + 1, 0);
-        if (K) {
-            HIP_CHECK(hipMemcpy(g->posId.data(), R.dPosId, K * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(g->posPos.data(), R.dPosPos, K * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(g->posCh.data(), R.dPosCh, K, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(g->posRevCh.data(), R.dPosRevCh, K, hipMemcpyDeviceToHost));
-        }
         if (C && N) HIP_CHECK(hipMemcpy(g->chrStart.data(), R.dChrStart, C * 8, hipMemcpyDeviceToHost));
         g->chrStart[C] = K;
         if (N) HIP_CHECK(hipMemcpy(&totals[1], R.dTotals + 1, 8, hipMemcpyDeviceToHost));
-        patched = totals[1];
-        B.download_bytes += 10 * K + 8 * C + 8;
+        B.download_bytes += 8 * C + 8;
         B.download_ms += nowMs() - td;
-        B.peak_device_bytes = R.peak;
-        X.peak_device_bytes = R.peak;
-    }   // (the device is released here: everything below is the host's)
-
-    // ---- the per-chromosome limit, and the letters the code bytes do not have
-    const double tp = nowMs();
-    const size_t C = g->chrStart.size() - 1;
-    for (size_t c = 0; c < C; c++) {
-        if (g->chrStart[c + 1] < g->chrStart[c]) throw LcbError(std::string(FN) + ": internal error: chrStart does not ascend");
-        if (g->chrStart[c + 1] - g->chrStart[c] >= LCB_SEG_POSITIONS) throw LcbError("a chromosome with 2^32 - 2^20 or more junctions is not supported (the reference's own limit is 2^32 bp, hence fewer than 2^32 junctions, per chromosome)");
+        for (size_t c = 0; c < C; c++) {
+            if (g->chrStart[c + 1] < g->chrStart[c]) throw LcbError(std::string(FN) + ": internal error: chrStart does not ascend");
+            if (g->chrStart[c + 1] - g->chrStart[c] >= LCB_SEG_POSITIONS) throw LcbError("a chromosome with 2^32 - 2^20 or more junctions is not supported (the reference's own limit is 2^32 bp, hence fewer than 2^32 junctions, per chromosome)");
+        }
+        B.kept_occurrences = (int64_t)K;
+        B.vertices = (int64_t)g->nVertex;
+        return totals[1];
     }
+}
+
+}  // namespace
+
+uint64_t lcb_graph_patch_chars(lcb_graph* g, int threads, std::vector<uint64_t>* patchQ, std::vector<uint8_t>* patchLetter)
+{
+    const size_t C = g->chrStart.size() - 1;
+    const int k = g->k;
+    std::vector<std::vector<uint64_t>> hits(patchQ ? C : 0);           // per chromosome: the list ascends without a sort
     uint64_t found = 0;
     #pragma omp parallel for num_threads(threads) schedule(dynamic, 1) reduction(+ : found)
     for (int64_t c = 0; c < (int64_t)C; c++) {
@@ -645,24 +646,97 @@ lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, in
         uint64_t i = g->chrStart[(size_t)c];
         const uint64_t end = g->chrStart[(size_t)c + 1];
         while (i < end) {
-            const uint8_t* hit = (const uint8_t*)memchr(ch + i, G_PATCH, end - i);
+            const uint8_t* hit = (const uint8_t*)memchr(ch + i, lcb_graphk::G_PATCH, end - i);
             if (!hit) break;
             i = (uint64_t)(hit - ch);
             ch[i] = (uint8_t)s[(size_t)g->posPos[i] + (size_t)k];
+            if (patchQ) hits[(size_t)c].push_back(i);
             found++;
             i++;
         }
     }
+    if (patchQ) {
+        patchQ->clear(); patchLetter->clear();
+        for (const std::vector<uint64_t>& h : hits)
+            for (uint64_t q : h) { patchQ->push_back(q); patchLetter->push_back(g->posCh[(size_t)q]); }
+    }
+    return found;
+}
+
+lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
+                                lcb_graph_build_stats* stats)
+{
+    const char* const FN = "lcb_graph_build";
+    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load", ordinal);
+    if (threads < 1) threads = 1;
+    lcb_graph_build_stats B;
+    memset(&B, 0, sizeof(B));
+    std::unique_ptr<lcb_graph> g(new lcb_graph());
+    uint64_t K = 0, patched = 0;
+    {
+        Run R;
+        patched = graphOnDevice(R, FN, g.get(), fasta, k, abundance, threads, ordinal, opts, B, K);
+
+        // ---- download: 10 bytes per kept occurrence
+        const double td = nowMs();
+        if (K) {
+            HIP_CHECK(hipMemcpy(g->posId.data(), R.dPosId, K * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g->posPos.data(), R.dPosPos, K * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g->posCh.data(), R.dPosCh, K, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g->posRevCh.data(), R.dPosRevCh, K, hipMemcpyDeviceToHost));
+        }
+        B.download_bytes += 10 * K;
+        B.download_ms += nowMs() - td;
+        B.peak_device_bytes = R.peak;
+        B.junctions.peak_device_bytes = R.peak;
+    }   // (the device is released here: everything below is the host's)
+
+    // ---- the letters the code bytes do not have
+    const double tp = nowMs();
+    const uint64_t found = lcb_graph_patch_chars(g.get(), threads);
     if (found != patched) throw LcbError(std::string(FN) + ": internal error: the device marked " + std::to_string(patched) + " characters for the host, " + std::to_string(found) + " were found");
     B.patched = (int64_t)patched;
     B.download_ms += nowMs() - tp;
 
     // ---- the host CSR, by the loader's code
-    t = nowMs();
+    const double t = nowMs();
     lcb_graph_build_csr(g.get(), threads);
     B.csr_ms = nowMs() - t;
-    B.kept_occurrences = (int64_t)K;
-    B.vertices = (int64_t)g->nVertex;
     if (stats) *stats = B;
     return g.release();
+}
+
+// ---- FASTA -> graph + device in one call: the same device part; then the junction run is released except for the
+// four kept arrays, which travel in a holder to the device that is being created (device.hip: placement, the one download, the patch
+// of both copies, the table build with the host CSR taken from it).
+void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal, const lcb_junction_opts_ex& jopts,
+                         const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats)
+{
+    const char* const FN = "lcb_open_fasta";
+    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load + lcb_device_create", ordinal);
+    if (threads < 1) threads = 1;
+    lcb_open_stats S;
+    memset(&S, 0, sizeof(S));
+    lcb_graph_build_stats& B = S.graph;
+    std::unique_ptr<lcb_graph> g(new lcb_graph());
+    LcbHandover ho;
+    ho.fn = FN; ho.threads = threads; ho.stats = &S;
+    uint64_t K = 0;
+    {
+        Run R;
+        ho.patched = graphOnDevice(R, FN, g.get(), fasta, k, abundance, threads, ordinal, jopts, B, K);
+        // the holder takes the four arrays out of the run's account; everything else of the run goes with it (raw arrays, counters,
+        // codes, record bases, stream and events)
+        ho.kept.release = [](void* q) { return (int)hipFree(q); };
+        ho.kept.K = K;
+        ho.kept.posId = LcbKeptArrays::take(R.dPosId); ho.kept.posPos = LcbKeptArrays::take(R.dPosPos);
+        ho.kept.posCh = LcbKeptArrays::take(R.dPosCh); ho.kept.posRevCh = LcbKeptArrays::take(R.dPosRevCh);
+        B.peak_device_bytes = R.peak;
+        B.junctions.peak_device_bytes = R.peak;
+        ho.junctionPeak = R.peak;
+    }
+    lcb_device* d = lcb_device_create_handover_impl(g.get(), p, ordinal, dopts, ho);
+    if (stats) *stats = S;
+    *graph = g.release();
+    *device = d;
 }

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lcb_host.h"
@@ -85,11 +86,73 @@ struct LcbTableJob {                 // what the build reads of a device that is
     void* (*alloc)(void* owner, size_t bytes);     // devAlloc / drop of the device that is being created
     void (*drop)(void* owner, void* p);
     void* owner;
+    struct LcbTableHandover* hand = nullptr;       // the hand-over route only (below)
+};
+// What the table build does on top on the hand-over route (lcb_open_fasta): the patch list goes up and handPatch writes
+// the device's posCh before anything reads it; once the sort has finished, the host CSR of `g` is taken from the scan (occStart), the
+// sorted payloads (occG) and handOccChr (occChr) instead of being computed on host threads.
+struct LcbTableHandover {
+    lcb_graph* g;                    // occStart / occG / occChr are filled
+    uint8_t* posCh;                  // the device's table
+    const uint64_t* patchQ;          // [nPatch] host: dense host positions ...
+    const uint8_t* patchLetter;      // ... and the letters that belong there
+    uint64_t nPatch;
+    double patchMs = 0, csrMs = 0;   // OUT: hipEvent-timed patch; wall time of handOccChr + the CSR copies + their widening
+    uint64_t csrBytes = 0;           // OUT: device -> host bytes of the CSR
+    uint64_t peakBytes = 0;          // OUT: most the build held at one time, occRec and the CSR's occChr included
 };
 void lcb_tables_need_impl(const char* fn, uint64_t bytes, const std::string& what);   // refuses a request beyond what hipMemGetInfo reports free, with both numbers
 void lcb_build_tables_impl(LcbTableJob& job, lcb_table_stats& stats);
 lcb_device* lcb_device_create_tables_impl(const lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, int tables, lcb_table_stats* stats);
 void lcb_device_table_read_impl(lcb_device* d, int table, uint64_t first, uint64_t n, void* out, uint64_t outBytes);
+
+// the hand-over route: junctions.hip builds the graph's arrays in HBM and passes them on, device.hip makes them its tables
+//
+// The four kept per-position arrays on their way from the junction run to the device that is being created. Movable, not copyable:
+// one owner at any moment. Whoever holds it when it dies frees what it still holds; the device takes an array out of it (take) in
+// the same step that registers it with its LcbOwner. Plain C++ without any HIP call: the maker says how an array is freed.
+struct LcbKeptArrays {
+    int32_t* posId = nullptr;
+    uint32_t* posPos = nullptr;
+    uint8_t *posCh = nullptr, *posRevCh = nullptr;
+    uint64_t K = 0;                          // kept positions; every array was made for max(1, K) elements
+    int (*release)(void*) = nullptr;         // hipFree in junctions.hip
+    LcbKeptArrays() = default;
+    LcbKeptArrays(const LcbKeptArrays&) = delete;
+    LcbKeptArrays& operator=(const LcbKeptArrays&) = delete;
+    LcbKeptArrays(LcbKeptArrays&& o) noexcept { *this = std::move(o); }
+    LcbKeptArrays& operator=(LcbKeptArrays&& o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            posId = o.posId; posPos = o.posPos; posCh = o.posCh; posRevCh = o.posRevCh; K = o.K; release = o.release;
+            o.posId = nullptr; o.posPos = nullptr; o.posCh = o.posRevCh = nullptr; o.K = 0;
+        }
+        return *this;
+    }
+    ~LcbKeptArrays() { reset(); }
+    template <class T>
+    static T* take(T*& p) { T* q = p; p = nullptr; return q; }      // the caller owns q from here on
+    bool empty() const { return !posId && !posPos && !posCh && !posRevCh; }
+    void reset()
+    {
+        for (void* p : {(void*)take(posId), (void*)take(posPos), (void*)take(posCh), (void*)take(posRevCh)})
+            if (p && release) (void)release(p);
+    }
+};
+struct LcbHandover {
+    const char* fn;                  // the call the messages name
+    LcbKeptArrays kept;
+    int threads;
+    uint64_t patched;                // characters the compaction marked for the host
+    uint64_t junctionPeak;           // peak of the junction run, by its own account
+    lcb_open_stats* stats;           // never null
+};
+// g: nVertex, chrStart, names and sequences are final, the four per-position vectors are sized and not yet filled, no CSR. On return
+// the graph is complete. Whatever way the call ends, `ho.kept` holds nothing.
+lcb_device* lcb_device_create_handover_impl(lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, LcbHandover& ho);
+void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal, const lcb_junction_opts_ex& jopts,
+                         const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats);
 
 // comm.hip — RCCL all-gather between the ranks of the round engine
 struct lcb_comm;

@@ -7,7 +7,9 @@
 // (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag, and so are the place where the seeds are
 // enumerated (LCB_SEEDS=host, the default, or device), the place where the device's tables are computed (LCB_TABLES=host, the
 // default, or device) and the way to the graph (LCB_JUNCTIONS=file, the default: the junction file of --graph; or device: the
-// junctions come from the FASTA arguments on the GPU, --graph is still required by the parser but never opened).
+// junctions come from the FASTA arguments on the GPU, --graph is still required by the parser but never opened) and the way the graph
+// reaches the device (LCB_HANDOVER=host, the default: the graph build releases the GPU and the device uploads its tables; or device,
+// which needs LCB_JUNCTIONS=device and one GPU: lcb_open_fasta, the graph's arrays stay in HBM and become the device's tables).
 // The block finder itself runs on the MI355X through the C ABI in include/lcb.h.
 #include <cstdio>
 #include <cstdlib>
@@ -140,6 +142,29 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    // ... and the way the graph reaches the device (LCB_HANDOVER=host, the default, or device: one call from the FASTA files to graph and device)
+    const char* handoverEnv = getenv("LCB_HANDOVER");
+    const std::string handoverRoute = handoverEnv && *handoverEnv ? handoverEnv : "host";
+    if (handoverRoute != "host" && handoverRoute != "device") {
+        std::cerr << "error: LCB_HANDOVER is '" << handoverRoute << "': it is host (the default) or device" << std::endl;
+        return 1;
+    }
+    const bool deviceHandover = handoverRoute == "device";
+    if (deviceHandover) {
+        const char* gpus = getenv("LCB_GPUS");
+        if (!deviceJunctions) {
+            std::cerr << "error: LCB_HANDOVER=device requires LCB_JUNCTIONS=device: it is the graph built on the device that is handed over" << std::endl;
+            return 1;
+        }
+        if (tablesEnv && *tablesEnv && !deviceTables) {
+            std::cerr << "error: LCB_HANDOVER=device together with LCB_TABLES=host is not supported: the tables of a handed-over graph are built on the device (LCB_TABLES unset or device)" << std::endl;
+            return 1;
+        }
+        if (gpus && *gpus && atoi(gpus) > 1) {
+            std::cerr << "error: LCB_HANDOVER=device together with LCB_GPUS=" << gpus << " is not supported: the graph is handed over to the device of a single-GPU run (LCB_GPUS unset or 1)" << std::endl;
+            return 1;
+        }
+    }
     lcb_graph* g = nullptr;
     lcb_device* dev = nullptr;
     lcb_gpus* set = nullptr;
@@ -151,7 +176,22 @@ int main(int argc, char** argv)
         std::cout << "Loading the graph..." << std::endl;                                      // sibeliaz.cpp:124
         std::vector<const char*> fa;
         for (auto& f : a.fasta) fa.push_back(f.c_str());
-        if (deviceJunctions) {
+        lcb_params p;
+        p.k = (int)a.k; p.min_block = (int)a.m; p.max_branch = (int)a.b; p.max_flank = (int)a.b;   // sibeliaz.cpp:133-138
+        p.looking_depth = 8; p.phase_size = 256;
+        if (deviceHandover) {
+            // graph and device in one call, on LCB_DEVICE: the device exists from here on, createDevices below finds it made
+            const char* ordEnv = getenv("LCB_DEVICE");
+            lcb_open_stats os;
+            if (lcb_open_fasta(fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t, &p, ordEnv && *ordEnv ? atoi(ordEnv) : 0, nullptr, nullptr, &g, &dev, &os) != LCB_OK) { fail(); break; }
+            if (getenv("LCB_VERBOSE"))
+                std::cerr << "lcb: handover=device records=" << os.graph.junctions.base.records << " raw=" << os.graph.raw_occurrences << " kept=" << os.graph.kept_occurrences
+                          << " vertices=" << os.graph.vertices << " patched=" << os.graph.patched << " download_bytes=" << os.graph.download_bytes << " upload_bytes=" << os.tables.upload_bytes
+                          << " csr_download_bytes=" << os.csr_download_bytes << " peak_device_bytes=" << os.peak_device_bytes << " parse_ms=" << os.graph.parse_ms
+                          << " compact_ms=" << os.graph.compact_ms << " place_ms=" << os.place_ms << " download_ms=" << os.graph.download_ms << " patch_ms=" << os.patch_ms
+                          << " window_ms=" << os.tables.window_ms << " csr_ms=" << os.tables.csr_ms << " sort_ms=" << os.tables.sort_ms << " csr_download_ms=" << os.csr_download_ms
+                          << " gather_ms=" << os.tables.gather_ms << std::endl;
+        } else if (deviceJunctions) {
             // on LCB_DEVICE (device 0 of an LCB_GPUS=N set); the graph is a host object and the build has released the device when it returns
             const char* ordEnv = getenv("LCB_DEVICE");
             const char* setEnv = getenv("LCB_GPUS");
@@ -168,9 +208,6 @@ int main(int argc, char** argv)
             g = lcb_graph_load(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t);
         if (!g) { fail(); break; }
         std::cout << "Analyzing the graph..." << std::endl;                                    // sibeliaz.cpp:132
-        lcb_params p;
-        p.k = (int)a.k; p.min_block = (int)a.m; p.max_branch = (int)a.b; p.max_flank = (int)a.b;   // sibeliaz.cpp:133-138
-        p.looking_depth = 8; p.phase_size = 256;
         // GPU selection comes from the environment, never from argv (the wrapper's command line, sibeliaz:146, stays as it is):
         // LCB_GPUS=N uses HIP devices 0..N-1 (as filtered by HIP_VISIBLE_DEVICES), LCB_DEVICE=i uses device i; default one GPU.
         // So does the seed route: LCB_SEEDS=host (default) enumerates with -t host threads before the device exists, LCB_SEEDS=device
@@ -179,6 +216,7 @@ int main(int argc, char** argv)
         const char* gpusEnv = getenv("LCB_GPUS");
         const int nGpus = gpusEnv && *gpusEnv ? atoi(gpusEnv) : 1;
         auto createDevices = [&]() -> bool {
+            if (dev) return true;             // (LCB_HANDOVER=device: made with the graph)
             if (nGpus > 1) {
                 std::vector<int> ord;
                 for (int i = 0; i < nGpus; i++) ord.push_back(i);

@@ -7,6 +7,8 @@
 //   csr       tableKeys (counts per vertex + the sort's input) -> tableScan over nVertex + 1 entries = occStart
 //   sort      tableDigitHist (all 4 digits) -> per digit that tells two keys apart: tableTileHist -> tableScan -> tableScatter
 //   gather    the sort's second buffers are released, occRec is made, tableGather fills it
+//   hand-over (lcb_open_fasta; LcbTableHandover): handPatch in front of the windows; between sort and gather the host CSR
+//             is downloaded - occStart, the sorted payloads, handOccChr of them (lcb_handover_kernels.h)
 //
 // Every temporary belongs to one Run, is made through the device's own allocator (devAlloc: registered with the device's owner),
 // checked against hipMemGetInfo before it is taken, and dropped before the call returns, whatever way it ends: createUsed and the
@@ -14,11 +16,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "lcb_device.h"
+#include "lcb_handover_kernels.h"
 #include "lcb_host.h"
 #include "lcb_segments.h"
 #include "lcb_table_kernels.h"
@@ -100,12 +104,35 @@ uint32_t gridFor(const char* fn, uint64_t items, uint64_t perBlock)
 template <class Q> struct K;
 template <> struct K<uint32_t> {
     static constexpr auto keys = tableKeys32; static constexpr auto scan = tableScan32; static constexpr auto tileHist = tableTileHist32;
-    static constexpr auto scatter = tableScatter32; static constexpr auto gather = tableGather32;
+    static constexpr auto scatter = tableScatter32; static constexpr auto gather = tableGather32; static constexpr auto occChr = lcb_handk::handOccChr32;
 };
 template <> struct K<unsigned long long> {
     static constexpr auto keys = tableKeys64; static constexpr auto scan = tableScan64; static constexpr auto tileHist = tableTileHist64;
-    static constexpr auto scatter = tableScatter64; static constexpr auto gather = tableGather64;
+    static constexpr auto scatter = tableScatter64; static constexpr auto gather = tableGather64; static constexpr auto occChr = lcb_handk::handOccChr64;
 };
+
+// (hand-over) n entries of Q from the device into the host's 64-bit vector: as they are, or widened chunk by chunk
+template <class Q>
+void drain(Run& R, const Q* src, uint64_t n, uint64_t* dst)
+{
+    if (!n) return;
+    if constexpr (sizeof(Q) == 8) {
+        HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n * 8, hipMemcpyDeviceToHost, R.stream));
+        HIP_CHECK(hipStreamSynchronize(R.stream));
+    } else {
+        const uint64_t chunk = std::min<uint64_t>(n, 1ull << 24);
+        std::vector<uint32_t> buf((size_t)chunk);
+        for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+            const int64_t m = (int64_t)std::min(chunk, n - c0);
+            HIP_CHECK(hipMemcpyAsync(buf.data(), src + c0, (size_t)m * 4, hipMemcpyDeviceToHost, R.stream));
+            HIP_CHECK(hipStreamSynchronize(R.stream));
+            const uint32_t* b = buf.data();
+            uint64_t* o = dst + c0;
+            #pragma omp parallel for schedule(static) if (m > (1 << 16))
+            for (int64_t i = 0; i < m; i++) o[i] = b[i];
+        }
+    }
+}
 
 template <class Q>
 void build(Run& R, lcb_table_stats& X)
@@ -116,10 +143,16 @@ void build(Run& R, lcb_table_stats& X)
     const uint64_t P = g.nPos(), V1 = (uint64_t)g.nVertex + 1, C = g.nChr();
     Q* occStart = (Q*)J.occStart;
     HIP_CHECK(hipMemsetAsync(occStart, 0, V1 * sizeof(Q), R.stream));
+    LcbTableHandover* const H = J.hand;
     if (!P) {                                                           // nothing survived the abundance filter: empty lists, no record
         J.occRec = J.alloc(J.owner, 1);
         HIP_CHECK(hipStreamSynchronize(R.stream));
         X.sort_passes_skipped = T_DIGITS;
+        if (H) {                                                        // (the cleared lists come down like any others; no kernel is launched)
+            H->g->occStart.resize((size_t)V1); H->g->occG.clear(); H->g->occChr.clear();
+            drain<Q>(R, occStart, V1, H->g->occStart.data());
+            H->csrBytes = sizeof(Q) * V1; H->peakBytes = 1;
+        }
         return;
     }
     const uint32_t nTiles = gridFor(J.fn, P, T_TILE);
@@ -137,6 +170,17 @@ void build(Run& R, lcb_table_stats& X)
     pl.nChr = (uint32_t)C;
     X.upload_bytes += planBytes;
     const uint32_t gridP = gridFor(J.fn, P, T_T);
+
+    // ---- (hand-over) the device's copy of the letters the host has patched in its own: before anything reads posCh - no table kernel does
+    if (H && H->nPatch) {
+        lcb_tables_need_impl(J.fn, H->nPatch * 9, "the patch list of " + std::to_string(H->nPatch) + " characters (9 bytes each)");
+        R.timed(H->patchMs, [&]() {
+            const unsigned long long* pq = R.upload<unsigned long long>(H->patchQ, (size_t)H->nPatch);
+            const uint8_t* pc = R.upload<uint8_t>(H->patchLetter, (size_t)H->nPatch);
+            lcb_handk::handPatch<<<gridFor(J.fn, H->nPatch, lcb_handk::H_T), lcb_handk::H_T, 0, R.stream>>>(pl, pq, pc, H->nPatch, P, H->posCh);
+        });
+        X.upload_bytes += H->nPatch * 9;
+    }
 
     R.timed(X.window_ms, [&]() { tableWindow<<<gridP, T_T, 0, R.stream>>>(pl, J.posPos, J.posWin, P, J.maxBranch); });
 
@@ -182,9 +226,29 @@ void build(Run& R, lcb_table_stats& X)
 
     // ---- gather: only the sorted payloads are still needed
     R.release(kin); R.release(kout); R.release(pout); R.release(tileHist);
+
+    // ---- (hand-over) the host CSR from what the device has just made: occStart = the scan's result, occG = the sorted payloads (the dense
+    // host position, ascending inside a vertex because the sort is stable: graph.cpp's order), occChr = handOccChr of them
+    if (H) {
+        const double t0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        lcb_graph& hg = *H->g;
+        lcb_tables_need_impl(J.fn, P * 4, "the chromosomes of " + std::to_string(P) + " occurrences (4 bytes each)");
+        uint32_t* occChr = R.alloc<uint32_t>(P * 4);
+        hipLaunchKernelGGL(K<Q>::occChr, dim3(gridP), dim3(lcb_handk::H_T), 0, R.stream, pl, (const Q*)pin, occChr, P);
+        HIP_CHECK(hipGetLastError());
+        hg.occStart.resize((size_t)V1); hg.occG.resize((size_t)P); hg.occChr.resize((size_t)P);
+        drain<Q>(R, occStart, V1, hg.occStart.data());
+        drain<Q>(R, pin, P, hg.occG.data());
+        HIP_CHECK(hipMemcpyAsync(hg.occChr.data(), occChr, (size_t)P * 4, hipMemcpyDeviceToHost, R.stream));
+        HIP_CHECK(hipStreamSynchronize(R.stream));
+        R.release(occChr);
+        H->csrBytes = (sizeof(Q) + 4) * P + sizeof(Q) * V1;
+        H->csrMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
+    }
     lcb_tables_need_impl(J.fn, P * 16, "the occurrence records of " + std::to_string(P) + " positions (16 bytes each)");
     uint4* rec = (uint4*)J.alloc(J.owner, (size_t)P * 16);
     J.occRec = rec;
+    if (H) H->peakBytes = std::max(R.peak, R.live + P * 16);
     R.timed(X.gather_ms, [&]() { hipLaunchKernelGGL(K<Q>::gather, dim3(gridP), dim3(T_T), 0, R.stream, pl, pin, J.posPos, J.posId, rec, P); });
 }
 
