@@ -357,6 +357,29 @@ int lcb_open_fasta(const char* const* fasta_files, int n_fasta, int k, int abund
                    const lcb_junction_opts_ex* jopts /* may be NULL */, const lcb_device_opts* dopts /* may be NULL */,
                    lcb_graph** graph, lcb_device** device, lcb_open_stats* stats /* may be NULL */);
 
+/* ---- a junction file opened on the GPU: the two calls above for the route that keeps the file - the `sibeliaz` wrapper
+ * runs `twopaco` and passes its junction file, whose vertex ids and order a drop-in has to keep. The file goes up as it is, 12 bytes
+ * per record, in tiles through two pinned buffers; separators, the largest |id|, the raw records and the first record of every
+ * chromosome are found by kernels; from the abundance counters on it is lcb_graph_build's code. The FASTA is parsed by the loader's
+ * parser. What lcb_graph_load refuses is refused with the same words: a chromosome without junctions in front of a later one,
+ * another number of FASTA records than chromosomes, a kept junction beyond the end of its sequence, kept positions that do not
+ * increase inside a chromosome.
+ * Of opts only abi, tile_windows (here: RECORDS PER UPLOAD TILE, default 2^22) and mem_budget are read; the result never depends on
+ * them. Stats: the structs of lcb_graph_build / lcb_open_fasta; junctions.base.records = chromosomes, read_ms = reading the file,
+ * upload_ms = file and code bytes (the counting kernels run inside it), take_ms = the scan of the separator counts and fileTake,
+ * abundance_ms, compact_ms (with the two checks) and download_* as in lcb_graph_build; the junction finder's fields are 0.
+ * One GPU, no CPU fallback: without a GPU both fail (the CPU way is lcb_graph_load). On error the outputs are NULL, and no device
+ * memory, pinned memory or file is left behind. */
+/* lcb_graph_load with the work on one MI355X: the same lcb_graph. */
+lcb_graph* lcb_graph_load_device(const char* junction_file, const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, int device_ordinal,
+                                 const lcb_junction_opts_ex* opts /* may be NULL */, lcb_graph_build_stats* stats /* may be NULL */);
+/* lcb_open_fasta for a junction file: graph and ready device in one call, the graph handed over in HBM. *graph and *device are exactly
+ * what lcb_graph_load followed by lcb_device_create_tables(g, p, ordinal, dopts, LCB_TABLES_DEVICE, ..) return: the same graph, host CSR
+ * included, the same bytes in all nine tables of lcb_device_table_read, the same options decided. */
+int lcb_open_junctions(const char* junction_file, const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, const lcb_params* p,
+                       int device_ordinal, const lcb_junction_opts_ex* jopts /* may be NULL */, const lcb_device_opts* dopts /* may be NULL */,
+                       lcb_graph** graph, lcb_device** device, lcb_open_stats* stats /* may be NULL */);
+
 /* THE HOT PATH: ProcessVertex::Process (blocksfinder.h:228-310) for a batch of seeds, each against the
  * device's current `used` state, one seed per workgroup (wavefront 0 runs the seed, the others share its look-ahead votes). offsets has n+1 entries; the instances of seed
  * i are inst[offsets[i] .. offsets[i+1]). Returns LCB_OK, or LCB_ERR (e.g. inst_cap too small: the needed

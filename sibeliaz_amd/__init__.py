@@ -6,4 +6,4 @@ the tests, `bench.py` and the multi-GPU driver; names mirror the reference class
 (JunctionStorage, BlocksFinder).
 """
 from .api import (LcbError, JunctionStorage, Device, GpuSet, Comm, Committer, BlocksFinder, Params, load_library, lib_path,  # noqa: F401
-                  SEED_DTYPE, INSTANCE_DTYPE, BLOCK_DTYPE, Hooks, build_junctions, JunctionOpts, JunctionStats, plan_junctions, JunctionOptsEx, JunctionStatsEx, GraphBuildStats, OpenStats, open_fasta)
+                  SEED_DTYPE, INSTANCE_DTYPE, BLOCK_DTYPE, Hooks, build_junctions, JunctionOpts, JunctionStats, plan_junctions, JunctionOptsEx, JunctionStatsEx, GraphBuildStats, OpenStats, open_fasta, open_junctions)

@@ -158,7 +158,7 @@ EXPORTS = [
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
     "lcb_generate_output", "lcb_comm_unique_id", "lcb_comm_create", "lcb_comm_destroy", "lcb_find_blocks_comm", "lcb_find_blocks_gpus", "lcb_gpus_create", "lcb_gpus_find_blocks", "lcb_gpus_destroy",
     "lcb_junctions_build", "lcb_junctions_build_ex", "lcb_junctions_plan", "lcb_device_enumerate_seeds", "lcb_device_sort_seeds", "lcb_gpus_device",
-    "lcb_device_create_tables", "lcb_device_table_read", "lcb_graph_build", "lcb_open_fasta",
+    "lcb_device_create_tables", "lcb_device_table_read", "lcb_graph_build", "lcb_open_fasta", "lcb_graph_load_device", "lcb_open_junctions",
 ]
 
 
@@ -182,6 +182,9 @@ def load_library():
     L.lcb_graph_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JunctionOptsEx), C.POINTER(GraphBuildStats)]
     L.lcb_open_fasta.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.POINTER(JunctionOptsEx), C.POINTER(DeviceOpts),
                                  C.POINTER(vp), C.POINTER(vp), C.POINTER(OpenStats)]
+    L.lcb_graph_load_device.restype = vp
+    L.lcb_graph_load_device.argtypes = [C.c_char_p] + L.lcb_graph_build.argtypes
+    L.lcb_open_junctions.argtypes = [C.c_char_p] + L.lcb_open_fasta.argtypes
     for f in ("lcb_graph_n_chr", "lcb_graph_n_pos", "lcb_graph_n_vertices"):
         getattr(L, f).restype = i64
         getattr(L, f).argtypes = [vp]
@@ -349,6 +352,31 @@ class JunctionStorage:
         self.k = k
         st = GraphBuildStats()
         self.h = self.L.lcb_graph_build(arr, len(files), int(k), int(abundance), int(threads), int(device), C.byref(o), C.byref(st))
+        if not self.h:
+            raise _err(self.L)
+        if not stats:
+            return self
+        out = {f: getattr(st.junctions.base, f) for f, _ in JunctionStats._fields_}
+        out.update({f: getattr(st.junctions, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
+        out.update({f: getattr(st, f) for f, _ in GraphBuildStats._fields_ if f != "junctions"})
+        return self, out
+
+    @classmethod
+    def load_device(cls, junction_file, fasta_files, k, abundance=150, threads=1, device=0, mem_budget=None, stats=False, **opts):
+        """JunctionStorage(junction_file, fasta_files, k, threads, abundance) with the work on one MI355X (lcb_graph_load_device): the file
+        goes up as it is, separators, abundance filter and compaction are kernels, the storage is the same. opts: tile_windows (records
+        per upload tile); mem_budget as in build - the storage never depends on them. stats=True: -> (storage, lcb_graph_build_stats as a
+        dict, flattened as build flattens it). No CPU fallback."""
+        o = _junction_opts(JunctionOptsEx, dict(opts, mem_budget=mem_budget or 0), ("abi", "tile_windows", "mem_budget"))
+        if isinstance(fasta_files, (str, bytes, os.PathLike)):
+            fasta_files = [fasta_files]
+        files = [os.fsencode(f) for f in fasta_files]
+        arr = (C.c_char_p * max(1, len(files)))(*files)
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.k = k
+        st = GraphBuildStats()
+        self.h = self.L.lcb_graph_load_device(os.fsencode(junction_file), arr, len(files), int(k), int(abundance), int(threads), int(device), C.byref(o), C.byref(st))
         if not self.h:
             raise _err(self.L)
         if not stats:
@@ -567,6 +595,36 @@ def open_fasta(fasta_files, k, params, abundance=150, threads=1, device=0, parti
     g, d, st = C.c_void_p(), C.c_void_p(), OpenStats()
     if L.lcb_open_fasta(arr, len(files), int(k), int(abundance), int(threads), C.byref(params), int(device), C.byref(o), C.byref(do), C.byref(g), C.byref(d), C.byref(st)):
         raise _err(L)
+    return _opened(L, k, params, g, d, st, stats)
+
+
+def open_junctions(junction_file, fasta_files, k, params, abundance=150, threads=1, device=0, mem_budget=None, stats=False, device_opts=None, **junction_opts):
+    """Junction file + FASTA files -> (JunctionStorage, Device) in one call on one MI355X (lcb_open_junctions): what
+    JunctionStorage(junction_file, fasta_files, k, threads, abundance) followed by Device(storage, params, device, tables="device",
+    **device_opts) gives - the same storage, the same bytes in every table of the device - with the file read on the GPU and the graph
+    handed over in HBM as open_fasta hands it over. junction_opts: tile_windows (records per upload tile); mem_budget as in
+    JunctionStorage.build; device_opts: a dict of lcb_device_opts fields. Close the device before the storage. stats=True: -> (storage,
+    device, lcb_open_stats as a dict, flattened as open_fasta flattens it). One GPU, no CPU fallback."""
+    o = _junction_opts(JunctionOptsEx, dict(junction_opts, mem_budget=mem_budget or 0), ("abi", "tile_windows", "mem_budget"))
+    do = DeviceOpts()
+    for name, v in (device_opts or {}).items():
+        if not hasattr(do, name):
+            raise TypeError("unknown device option %r" % name)
+        setattr(do, name, int(v))
+    if isinstance(fasta_files, (str, bytes, os.PathLike)):
+        fasta_files = [fasta_files]
+    files = [os.fsencode(f) for f in fasta_files]
+    arr = (C.c_char_p * max(1, len(files)))(*files)
+    L = load_library()
+    g, d, st = C.c_void_p(), C.c_void_p(), OpenStats()
+    if L.lcb_open_junctions(os.fsencode(junction_file), arr, len(files), int(k), int(abundance), int(threads), C.byref(params), int(device), C.byref(o), C.byref(do),
+                            C.byref(g), C.byref(d), C.byref(st)):
+        raise _err(L)
+    return _opened(L, k, params, g, d, st, stats)
+
+
+def _opened(L, k, params, g, d, st, stats):
+    """The handles and the lcb_open_stats of lcb_open_fasta / lcb_open_junctions as Python objects."""
     storage = JunctionStorage.__new__(JunctionStorage)
     storage.L, storage.k, storage.h = L, k, g.value
     dev = Device.__new__(Device)

@@ -23,7 +23,7 @@ LIB = os.path.join(PKG, "libsibeliaz_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 LIB_SRC = ["graph.cpp", "bundles.cpp", "commit.cpp", "engine.cpp", "output.cpp", "capi.cpp", "junction_plan.cpp", "comm.hip", "device.hip", "junctions.hip", "seeds.hip", "tables.hip"]
-LIB_HDR = ["lcb_host.h", "lcb_kernel.h", "lcb_device.h", "lcb_segments.h", "lcb_kernel_limits.h", "lcb_fasta.h", "lcb_junction_kernels.h", "lcb_seed_kernels.h", "lcb_table_kernels.h", "lcb_graph_kernels.h", "lcb_handover_kernels.h", "lcb_owned.h"]
+LIB_HDR = ["lcb_host.h", "lcb_kernel.h", "lcb_device.h", "lcb_segments.h", "lcb_kernel_limits.h", "lcb_fasta.h", "lcb_junction_kernels.h", "lcb_seed_kernels.h", "lcb_table_kernels.h", "lcb_graph_kernels.h", "lcb_handover_kernels.h", "lcb_owned.h", "lcb_file_kernels.h", "lcb_file_host.h"]
 
 
 def _newer(srcs, out):

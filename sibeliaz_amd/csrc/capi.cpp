@@ -188,6 +188,62 @@ int lcb_open_fasta(const char* const* fasta_files, int n_fasta, int k, int abund
     LCB_CATCH(LCB_ERR)
 }
 
+namespace {
+// The arguments of the two calls that open a junction file on the device; what can be said without a device is said before one is
+// looked for, with the loader's words where the loader has them. fa: the FASTA paths.
+void fileArgs(const std::string& fn, const char* junction_file, const char* const* fasta_files, int n_fasta, int k, const lcb_junction_opts_ex* opts, std::vector<std::string>& fa)
+{
+    if (!junction_file || !fasta_files || n_fasta <= 0) throw LcbError(fn + ": missing input files");
+    if (k <= 0 || (k % 2) == 0) throw LcbError("value of K must be odd");
+    checkJunctionOpts(opts, "lcb_junction_opts_ex");
+    for (int i = 0; i < n_fasta; i++) {
+        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
+        fa.push_back(fasta_files[i]);
+    }
+    FILE* f = fopen(junction_file, "rb");
+    if (!f) throw LcbError("Can't read the input file");
+    fclose(f);
+    for (const std::string& s : fa) {
+        f = fopen(s.c_str(), "rb");
+        if (!f) throw LcbError("Can't open file " + s);
+        fclose(f);
+    }
+}
+}  // namespace
+
+lcb_graph* lcb_graph_load_device(const char* junction_file, const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, int device_ordinal,
+                                 const lcb_junction_opts_ex* opts, lcb_graph_build_stats* stats)
+{
+    LCB_TRY
+    std::vector<std::string> fa;
+    fileArgs("lcb_graph_load_device", junction_file, fasta_files, n_fasta, k, opts, fa);
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    return lcb_graph_load_device_impl(junction_file, fa, k, abundance, threads, device_ordinal, opts ? *opts : o, stats);
+    LCB_CATCH(nullptr)
+}
+
+int lcb_open_junctions(const char* junction_file, const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, const lcb_params* p, int device_ordinal,
+                       const lcb_junction_opts_ex* jopts, const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats)
+{
+    if (graph) *graph = nullptr;
+    if (device) *device = nullptr;
+    LCB_TRY
+    const std::string fn = "lcb_open_junctions";
+    if (!graph || !device || !p) throw LcbError(fn + ": null argument");
+    checkAbi(nullptr, dopts);
+    if (p->max_branch >= 65000 || p->looking_depth >= 65000) throw LcbError("maxBranchSize / lookingDepth of 65000 or more are not supported by the device vote table");
+    std::vector<std::string> fa;
+    fileArgs(fn, junction_file, fasta_files, n_fasta, k, jopts, fa);
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    lcb_open_junctions_impl(junction_file, fa, k, abundance, threads, p, device_ordinal, jopts ? *jopts : o, dopts, graph, device, stats);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
+
 int lcb_junctions_plan(int64_t windows, int64_t seq_bytes, const lcb_junction_opts_ex* opts, uint64_t budget, int32_t* partitions, uint64_t* need_bytes)
 {
     LCB_TRY

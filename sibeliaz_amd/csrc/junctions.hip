@@ -17,6 +17,9 @@
 //   sinks      the pipeline (junctionPipeline) has two callers. lcb_junctions_build_impl copies a tile's records to the host and writes
 //              the junction file; lcb_graph_build_impl keeps them in HBM and makes the graph of them with the kernels of
 //              lcb_graph_kernels.h - what lcb_graph_load makes of the file, without the file.
+//   file       the tail of that graph build (graphTail: abundance, keep-count, scan, compaction) has a second front half: a junction
+//              file read on the device (graphFromFile, kernels in lcb_file_kernels.h) puts the file's records where
+//              graphTake puts the junction finder's. No k-mer table, no pipeline: lcb_graph_load with the work on the GPU.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +33,8 @@
 
 #include "lcb_device.h"
 #include "lcb_fasta.h"
+#include "lcb_file_host.h"
+#include "lcb_file_kernels.h"
 #include "lcb_graph_kernels.h"
 #include "lcb_host.h"
 #include "lcb_junction_kernels.h"
@@ -78,6 +83,9 @@ struct Run {
     uint32_t* dPosPos = nullptr;
     uint8_t *dPosCh = nullptr, *dPosRevCh = nullptr;
     uint8_t* hStage[2] = {nullptr, nullptr};
+    // the junction file opened on the device (lcb_graph_load_device_impl): its words, the separators per workgroup, the two flags
+    uint32_t* dFile = nullptr;
+    unsigned long long *dBlockSep = nullptr, *dFlags = nullptr;
     std::string fn = "lcb_junctions_build";      // the call the messages name
     uint64_t budget = 0, live = 0, peak = 0;     // the run's own account of its device memory
     uint64_t tableBytesKey = 0, tableBytesVal = 0, tileBytes[4] = {0, 0, 0, 0}, bitmapBytes = 0;   // what the pipeline holds when it returns
@@ -86,7 +94,7 @@ struct Run {
         if (stream) (void)hipStreamSynchronize(stream);
         for (void* p : {(void*)dCodes, (void*)dKey, (void*)dVal, (void*)dBitmap, (void*)dWslot, (void*)dOut, (void*)dCntJ, (void*)dCntF, (void*)dState, (void*)dRawPos,
                         (void*)dRawId, (void*)dBase, (void*)dRecFirst, (void*)dBlockKept, (void*)dChrStart, (void*)dTotals, (void*)dCounter, (void*)dPosId, (void*)dPosPos,
-                        (void*)dPosCh, (void*)dPosRevCh})
+                        (void*)dPosCh, (void*)dPosRevCh, (void*)dFile, (void*)dBlockSep, (void*)dFlags})
             if (p) (void)hipFree(p);
         if (hState) (void)hipHostFree(hState);
         for (JRecord* p : hOut) if (p) (void)hipHostFree(p);
@@ -95,6 +103,15 @@ struct Run {
         if (stream) (void)hipStreamDestroy(stream);
         if (f) fclose(f);
         if (!part.empty()) remove(part.c_str());
+    }
+    // The stream and the events of the run.
+    void start()
+    {
+        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        HIP_CHECK(hipEventCreate(&evA));
+        HIP_CHECK(hipEventCreate(&evB));
+        HIP_CHECK(hipEventCreate(&evCopy[0]));
+        HIP_CHECK(hipEventCreate(&evCopy[1]));
     }
     // Would `bytes` more fit? Against the budget by the run's own account, and against what the device reports free.
     bool fits(uint64_t bytes) const
@@ -248,11 +265,7 @@ uint64_t junctionPipeline(Run& R, const Source& src, int k, int ordinal, const l
                        (P == 1 ? "24 bytes per tile window)" : "one bit per base)"));
     X.partitions = P;
 
-    HIP_CHECK(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreate(&R.evA));
-    HIP_CHECK(hipEventCreate(&R.evB));
-    HIP_CHECK(hipEventCreate(&R.evCopy[0]));
-    HIP_CHECK(hipEventCreate(&R.evCopy[1]));
+    R.start();
     R.alloc(R.dCodes, len, "the sequence");
     R.alloc(R.dState, LCB_JUNCTION_STATE_BYTES, "the state");
     auto allocTiles = [&]() {
@@ -476,9 +489,55 @@ void lcb_junctions_build_impl(const std::vector<std::string>& fasta, int k, int 
 // lcb_open_fasta_impl passes them on to the device that is being created.
 namespace {
 
-// Parse, junction pipeline, abundance filter, compaction: on return R holds the four kept arrays (K positions each) besides what is
-// left of the run, g has its names, sequences, nVertex and chrStart, and its per-position vectors have their size (nothing in them
-// yet). The per-chromosome limit is checked. -> the characters the compaction marked for the host (the sentinel in posCh).
+// The FASTA files with the loader's parser (the strings stay in the graph) -> where the records lie in the code array.
+Source parseSource(const char* const FN, lcb_graph* g, const std::vector<std::string>& fasta, int k, int threads)
+{
+    g->k = k;
+    const size_t nRec = lcb_graph_parse_fasta(*g, fasta, threads);
+    Source src;
+    for (size_t r = 0; r < nRec; r++) src.recLen.push_back(g->seq[r].size());
+    src.layout(k);
+    if (nRec > 0x7FFFFFFFull) throw LcbError(std::string(FN) + ": more than 2^31 - 1 FASTA records");
+    return src;
+}
+
+// The code bytes of the graph's strings -> R.dCodes (which holds a breaker everywhere): made chunk by chunk in the run's two pinned
+// staging buffers (never in place: the strings are the graph's) and copied behind each other.
+void uploadCodes(Run& R, const lcb_graph* g, const Source& src, int threads)
+{
+    const std::vector<uint64_t>& base = src.base;
+    const uint64_t len = src.len;
+    const size_t nRec = src.recLen.size();
+    const uint64_t chunk = std::min<uint64_t>(len, 32ull << 20);
+    for (uint8_t*& p : R.hStage) HIP_CHECK(hipHostMalloc((void**)&p, chunk, hipHostMallocDefault));
+    size_t r = 0;
+    int64_t n = 0;
+    for (uint64_t c0 = 0; c0 < len; c0 += chunk, n++) {
+        const int slot = (int)(n & 1);
+        if (n >= 2) HIP_CHECK(hipEventSynchronize(R.evCopy[slot]));
+        uint8_t* s = R.hStage[slot];
+        const uint64_t c1 = std::min(len, c0 + chunk);
+        memset(s, 4, c1 - c0);
+        while (r < nRec && base[r] + src.recLen[r] <= c0) r++;
+        for (size_t q = r; q < nRec && base[q] < c1; q++) {
+            const int64_t lo = (int64_t)std::max(base[q], c0), hi = (int64_t)std::min(base[q] + src.recLen[q], c1);
+            const char* p = g->seq[q].data();
+            const int64_t b = (int64_t)base[q], s0 = (int64_t)c0;
+            #pragma omp parallel for num_threads(threads) schedule(static) if (hi - lo > (1 << 16))
+            for (int64_t i = lo; i < hi; i++) { const int c = lcb_fasta::code(p[i - b]); s[i - s0] = (uint8_t)(c < 0 ? 4 : c); }
+        }
+        HIP_CHECK(hipMemcpyAsync(R.dCodes + c0, s, c1 - c0, hipMemcpyHostToDevice, R.stream));
+        HIP_CHECK(hipEventRecord(R.evCopy[slot], R.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(R.stream));
+    for (uint8_t*& p : R.hStage) { HIP_CHECK(hipHostFree(p)); p = nullptr; }
+}
+
+uint64_t graphTail(Run& R, const char* const FN, lcb_graph* g, uint64_t N, size_t runs, size_t nRec, int k, int abundance, bool fromFile, lcb_graph_build_stats& B,
+                   uint64_t& K);
+
+// The front half for the FASTA files alone: parse, junction pipeline with a sink that keeps a tile's records on the device (graphTake),
+// then the tail. -> what the tail returns.
 uint64_t graphOnDevice(Run& R, const char* const FN, lcb_graph* g, const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal,
                        const lcb_junction_opts_ex& opts, lcb_graph_build_stats& B, uint64_t& K)
 {
@@ -487,46 +546,17 @@ uint64_t graphOnDevice(Run& R, const char* const FN, lcb_graph* g, const std::ve
 
     // ---- parse once, with the loader's parser; the strings stay in the graph
     double t = nowMs();
-    g->k = k;
-    const size_t nRec = lcb_graph_parse_fasta(*g, fasta, threads);
-    Source src;
-    for (size_t r = 0; r < nRec; r++) src.recLen.push_back(g->seq[r].size());
-    src.layout(k);
-    if (nRec > 0x7FFFFFFFull) throw LcbError(std::string(FN) + ": more than 2^31 - 1 FASTA records");
+    Source src = parseSource(FN, g, fasta, k, threads);
+    const size_t nRec = src.recLen.size();
     const std::vector<uint64_t>& base = src.base;
-    const uint64_t len = src.len;
     B.parse_ms = nowMs() - t;
 
     uint64_t N = 0, ids = 0;
-    std::vector<unsigned long long> recFirst(nRec);
     {
         R.fn = FN;
-        // the code bytes, made chunk by chunk in pinned memory (never in place: the strings are the graph's) and copied behind each other
         src.upload = [&](Run& R) {
             const double t0 = nowMs();
-            const uint64_t chunk = std::min<uint64_t>(len, 32ull << 20);
-            for (uint8_t*& p : R.hStage) HIP_CHECK(hipHostMalloc((void**)&p, chunk, hipHostMallocDefault));
-            size_t r = 0;
-            int64_t n = 0;
-            for (uint64_t c0 = 0; c0 < len; c0 += chunk, n++) {
-                const int slot = (int)(n & 1);
-                if (n >= 2) HIP_CHECK(hipEventSynchronize(R.evCopy[slot]));
-                uint8_t* s = R.hStage[slot];
-                const uint64_t c1 = std::min(len, c0 + chunk);
-                memset(s, 4, c1 - c0);
-                while (r < nRec && base[r] + src.recLen[r] <= c0) r++;
-                for (size_t q = r; q < nRec && base[q] < c1; q++) {
-                    const int64_t lo = (int64_t)std::max(base[q], c0), hi = (int64_t)std::min(base[q] + src.recLen[q], c1);
-                    const char* p = g->seq[q].data();
-                    const int64_t b = (int64_t)base[q], s0 = (int64_t)c0;
-                    #pragma omp parallel for num_threads(threads) schedule(static) if (hi - lo > (1 << 16))
-                    for (int64_t i = lo; i < hi; i++) { const int c = lcb_fasta::code(p[i - b]); s[i - s0] = (uint8_t)(c < 0 ? 4 : c); }
-                }
-                HIP_CHECK(hipMemcpyAsync(R.dCodes + c0, s, c1 - c0, hipMemcpyHostToDevice, R.stream));
-                HIP_CHECK(hipEventRecord(R.evCopy[slot], R.stream));
-            }
-            HIP_CHECK(hipStreamSynchronize(R.stream));
-            for (uint8_t*& p : R.hStage) { HIP_CHECK(hipHostFree(p)); p = nullptr; }
+            uploadCodes(R, g, src, threads);
             B.parse_ms += nowMs() - t0;
         };
         Sink sink;
@@ -558,77 +588,100 @@ uint64_t graphOnDevice(Run& R, const char* const FN, lcb_graph* g, const std::ve
         R.release(R.dOut, R.tileBytes[1]);
         R.release(R.dCntJ, R.tileBytes[2]);
         R.release(R.dCntF, R.tileBytes[3]);
-
-        // ---- what the loader refuses in a junction file: a chromosome without junctions in front of a later one; records behind the
-        // last chromosome (a junction file has no way to say that they exist)
-        double td = nowMs();
-        if (nRec) HIP_CHECK(hipMemcpy(recFirst.data(), R.dRecFirst, nRec * 8, hipMemcpyDeviceToHost));
-        B.download_bytes += nRec * 8;
-        size_t C = 0;
-        while (C < nRec && recFirst[C] != G_NONE) C++;
-        for (size_t r = C; r < nRec; r++)
-            if (recFirst[r] != G_NONE) throw LcbError("the junction file has a chromosome without junctions (unsupported)");
-        if (C < nRec) throw LcbError("the FASTA input has more records than the junction file has chromosomes");
-        for (size_t c = 0; c < C; c++)
-            if (recFirst[c] >= N || (c ? recFirst[c] <= recFirst[c - 1] : recFirst[c] != 0)) throw LcbError(std::string(FN) + ": internal error: the first raw indices of the records do not ascend");
-        B.download_ms += nowMs() - td;
-        g->nVertex = N ? (uint32_t)(ids + 1) : 0u;
-
-        // ---- abundance over the unfiltered records of both strands, keep-counts, their scan
-        const uint32_t nb = N ? gridFor(N, G_T, FN) : 0;
-        R.alloc(R.dCounter, ((uint64_t)g->nVertex + 1) * sizeof(uint32_t), "the abundance counters");
-        R.alloc(R.dBlockKept, ((uint64_t)nb + 1) * 8, "the keep-counts");
-        R.alloc(R.dTotals, 16, "the totals");
-        const char* aggEnv = getenv("LCB_GRAPH_ABUNDANCE");          // wave (aggregate equal ids within a wavefront) or plain; a measurement hook
-        const bool wave = aggEnv && std::string(aggEnv) == "wave";
-        R.timed(B.abundance_ms, [&]() {
-            HIP_CHECK(hipMemsetAsync(R.dCounter, 0, ((uint64_t)g->nVertex + 1) * sizeof(uint32_t), R.stream));
-            HIP_CHECK(hipMemsetAsync(R.dTotals, 0, 16, R.stream));
-            if (!N) return;
-            if (wave) graphAbundanceWave<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter);
-            else graphAbundance<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter);
-        });
-        unsigned long long totals[2] = {0, 0};
-        if (N) {
-            R.timed(B.compact_ms, [&]() {
-                graphKeepCount<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBlockKept);
-                graphScan<<<1, G_SCAN_T, 0, R.stream>>>(R.dBlockKept, nb, R.dTotals);
-            });
-            HIP_CHECK(hipMemcpy(totals, R.dTotals, 8, hipMemcpyDeviceToHost));
-            B.download_bytes += 8;
-        }
-        K = totals[0];
-        if (K > N) throw LcbError(std::string(FN) + ": internal error: more kept than raw occurrences");
-
-        // ---- compaction: the four per-position arrays and chrStart
-        R.alloc(R.dPosId, std::max<uint64_t>(1, K) * 4, "the kept ids");
-        R.alloc(R.dPosPos, std::max<uint64_t>(1, K) * 4, "the kept positions");
-        R.alloc(R.dPosCh, std::max<uint64_t>(1, K), "the characters");
-        R.alloc(R.dPosRevCh, std::max<uint64_t>(1, K), "the characters");
-        R.alloc(R.dChrStart, (C + 1) * 8, "chrStart");
-        if (N)
-            R.timed(B.compact_ms, [&]() {
-                graphCompact<<<nb, G_T, 0, R.stream>>>(R.dRawPos, R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBlockKept, R.dCodes, R.dBase, R.dRecFirst, (uint32_t)C, k,
-                                                       R.dPosId, R.dPosPos, R.dPosCh, R.dPosRevCh, R.dChrStart, R.dTotals + 1);
-            });
-
-        // ---- download: chrStart, the number of characters to patch (both tiny); the per-chromosome limit
-        td = nowMs();
-        g->posId.resize(K); g->posPos.resize(K); g->posCh.resize(K); g->posRevCh.resize(K);
-        g->chrStart.assign(C + 1, 0);
-        if (C && N) HIP_CHECK(hipMemcpy(g->chrStart.data(), R.dChrStart, C * 8, hipMemcpyDeviceToHost));
-        g->chrStart[C] = K;
-        if (N) HIP_CHECK(hipMemcpy(&totals[1], R.dTotals + 1, 8, hipMemcpyDeviceToHost));
-        B.download_bytes += 8 * C + 8;
-        B.download_ms += nowMs() - td;
-        for (size_t c = 0; c < C; c++) {
-            if (g->chrStart[c + 1] < g->chrStart[c]) throw LcbError(std::string(FN) + ": internal error: chrStart does not ascend");
-            if (g->chrStart[c + 1] - g->chrStart[c] >= LCB_SEG_POSITIONS) throw LcbError("a chromosome with 2^32 - 2^20 or more junctions is not supported (the reference's own limit is 2^32 bp, hence fewer than 2^32 junctions, per chromosome)");
-        }
-        B.kept_occurrences = (int64_t)K;
-        B.vertices = (int64_t)g->nVertex;
-        return totals[1];
     }
+    g->nVertex = N ? (uint32_t)(ids + 1) : 0u;
+    return graphTail(R, FN, g, N, nRec, nRec, k, abundance, false, B, K);
+}
+
+// The tail of its two front halves (the FASTA files alone, above; a junction file, graphFromFile below): abundance filter and compaction.
+// In: R holds the N raw records (dRawPos, dRawId), the first raw index of each of the `runs` runs of records (dRecFirst; a run is a FASTA
+// record that has junctions, or what lies between two separators of a file), the code bytes and the bases of the nRec FASTA records
+// (dCodes, dBase); g has its names, sequences and nVertex. On return R holds the four kept arrays (K positions each) besides what is
+// left of the run, g has chrStart, and its per-position vectors have their size (nothing in them yet). The per-chromosome limit is
+// checked; fromFile: so is what a junction finder of ours cannot get wrong (fileBounds, fileOrder). -> the characters the compaction
+// marked for the host (the sentinel in posCh).
+uint64_t graphTail(Run& R, const char* const FN, lcb_graph* g, uint64_t N, size_t runs, size_t nRec, int k, int abundance, bool fromFile, lcb_graph_build_stats& B,
+                   uint64_t& K)
+{
+    using namespace lcb_graphk;
+    // ---- what the loader refuses in a junction file: a chromosome without junctions in front of a later one; another number of
+    // FASTA records than chromosomes (a junction file has no way to say that records behind the last chromosome exist)
+    double td = nowMs();
+    std::vector<unsigned long long> recFirst(runs);
+    if (runs) HIP_CHECK(hipMemcpy(recFirst.data(), R.dRecFirst, runs * 8, hipMemcpyDeviceToHost));
+    B.download_bytes += runs * 8;
+    const size_t C = lcb_file::chromosomes(recFirst.data(), runs, N);
+    lcb_file::sameRecords(nRec, C);
+    B.junctions.base.records = (int64_t)C;
+    B.download_ms += nowMs() - td;
+
+    // ---- abundance over the unfiltered records of both strands, keep-counts, their scan
+    const uint32_t nb = N ? gridFor(N, G_T, FN) : 0;
+    R.alloc(R.dCounter, ((uint64_t)g->nVertex + 1) * sizeof(uint32_t), "the abundance counters");
+    R.alloc(R.dBlockKept, ((uint64_t)nb + 1) * 8, "the keep-counts");
+    R.alloc(R.dTotals, 16, "the totals");
+    const char* aggEnv = getenv("LCB_GRAPH_ABUNDANCE");          // wave (aggregate equal ids within a wavefront) or plain; a measurement hook
+    const bool wave = aggEnv && std::string(aggEnv) == "wave";
+    R.timed(B.abundance_ms, [&]() {
+        HIP_CHECK(hipMemsetAsync(R.dCounter, 0, ((uint64_t)g->nVertex + 1) * sizeof(uint32_t), R.stream));
+        HIP_CHECK(hipMemsetAsync(R.dTotals, 0, 16, R.stream));
+        if (!N) return;
+        if (wave) graphAbundanceWave<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter);
+        else graphAbundance<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter);
+    });
+    unsigned long long totals[2] = {0, 0}, flags[2] = {0, 0};      // (R.dFlags: the front half of a file made and cleared it)
+    if (N) {
+        R.timed(B.compact_ms, [&]() {
+            graphKeepCount<<<nb, G_T, 0, R.stream>>>(R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBlockKept);
+            graphScan<<<1, G_SCAN_T, 0, R.stream>>>(R.dBlockKept, nb, R.dTotals);
+            // a kept junction beyond the end of its sequence is refused before the compaction reads the code bytes around it
+            if (fromFile) lcb_filek::fileBounds<<<nb, G_T, 0, R.stream>>>(R.dRawPos, R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBase, R.dRecFirst, (uint32_t)C, k, R.dFlags);
+        });
+        HIP_CHECK(hipMemcpy(totals, R.dTotals, 8, hipMemcpyDeviceToHost));
+        B.download_bytes += 8;
+        if (fromFile) {
+            HIP_CHECK(hipMemcpy(flags, R.dFlags, 8, hipMemcpyDeviceToHost));
+            B.download_bytes += 8;
+            if (flags[0]) throw LcbError("a junction lies beyond the end of its sequence (junction file and FASTA do not match)");
+        }
+    }
+    K = totals[0];
+    if (K > N) throw LcbError(std::string(FN) + ": internal error: more kept than raw occurrences");
+
+    // ---- compaction: the four per-position arrays and chrStart
+    R.alloc(R.dPosId, std::max<uint64_t>(1, K) * 4, "the kept ids");
+    R.alloc(R.dPosPos, std::max<uint64_t>(1, K) * 4, "the kept positions");
+    R.alloc(R.dPosCh, std::max<uint64_t>(1, K), "the characters");
+    R.alloc(R.dPosRevCh, std::max<uint64_t>(1, K), "the characters");
+    R.alloc(R.dChrStart, (C + 1) * 8, "chrStart");
+    if (N)
+        R.timed(B.compact_ms, [&]() {
+            graphCompact<<<nb, G_T, 0, R.stream>>>(R.dRawPos, R.dRawId, N, R.dCounter, (uint32_t)abundance, R.dBlockKept, R.dCodes, R.dBase, R.dRecFirst, (uint32_t)C, k,
+                                                   R.dPosId, R.dPosPos, R.dPosCh, R.dPosRevCh, R.dChrStart, R.dTotals + 1);
+            if (fromFile && K > 1) lcb_filek::fileOrder<<<gridFor(K, G_T, FN), G_T, 0, R.stream>>>(R.dPosPos, K, R.dChrStart, (uint32_t)C, R.dFlags);
+        });
+    if (fromFile && K > 1) {
+        HIP_CHECK(hipMemcpy(&flags[1], R.dFlags + 1, 8, hipMemcpyDeviceToHost));
+        B.download_bytes += 8;
+        if (flags[1]) throw LcbError("junction positions must strictly increase within a chromosome");
+    }
+
+    // ---- download: chrStart, the number of characters to patch (both tiny); the per-chromosome limit
+    td = nowMs();
+    g->posId.resize(K); g->posPos.resize(K); g->posCh.resize(K); g->posRevCh.resize(K);
+    g->chrStart.assign(C + 1, 0);
+    if (C && N) HIP_CHECK(hipMemcpy(g->chrStart.data(), R.dChrStart, C * 8, hipMemcpyDeviceToHost));
+    g->chrStart[C] = K;
+    if (N) HIP_CHECK(hipMemcpy(&totals[1], R.dTotals + 1, 8, hipMemcpyDeviceToHost));
+    B.download_bytes += 8 * C + 8;
+    B.download_ms += nowMs() - td;
+    for (size_t c = 0; c < C; c++) {
+        if (g->chrStart[c + 1] < g->chrStart[c]) throw LcbError(std::string(FN) + ": internal error: chrStart does not ascend");
+        if (g->chrStart[c + 1] - g->chrStart[c] >= LCB_SEG_POSITIONS) throw LcbError("a chromosome with 2^32 - 2^20 or more junctions is not supported (the reference's own limit is 2^32 bp, hence fewer than 2^32 junctions, per chromosome)");
+    }
+    B.kept_occurrences = (int64_t)K;
+    B.vertices = (int64_t)g->nVertex;
+    return totals[1];
 }
 
 }  // namespace
@@ -663,11 +716,104 @@ uint64_t lcb_graph_patch_chars(lcb_graph* g, int threads, std::vector<uint64_t>*
     return found;
 }
 
-lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
-                                lcb_graph_build_stats* stats)
+namespace {
+
+// ---- the front half for a junction file: what lcb_graph_load_impl reads on host threads, read on the device. The file
+// goes up tile by tile through the run's two pinned staging buffers and stays resident as words until its records are taken:
+// fileCount per tile (the host reads tile n + 1 meanwhile), a scan, fileTake; then the file is released, the FASTA is parsed, its code
+// bytes go up, and the tail runs. Of `opts`, tile_windows (records per tile) and mem_budget are read. -> what the tail returns.
+uint64_t graphFromFile(Run& R, const char* const FN, lcb_graph* g, const std::string& file, const std::vector<std::string>& fasta, int k, int abundance, int threads,
+                       int ordinal, const lcb_junction_opts_ex& opts, lcb_graph_build_stats& B, uint64_t& K)
 {
-    const char* const FN = "lcb_graph_build";
-    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load", ordinal);
+    using namespace lcb_filek;
+    lcb_junction_stats& S = B.junctions.base;
+    R.fn = FN;
+    lcb_file::Reader in(file);
+    const lcb_file::Tiling T = lcb_file::tiling(in.bytes, opts.tile_windows);
+    const uint64_t blocks = T.blocks();
+    HIP_CHECK(hipSetDevice(ordinal));
+    size_t freeB = 0, totalB = 0;
+    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+    R.budget = opts.mem_budget ? std::min<uint64_t>(opts.mem_budget, freeB) : (uint64_t)freeB;
+    R.start();
+    R.alloc(R.dState, LCB_JUNCTION_STATE_BYTES, "the state");
+    R.alloc(R.dFlags, 32, "the counts and the flags of the file");       // [0] fileBounds, [1] fileOrder, [2] separators, [3] max |id| + 1
+    R.alloc(R.dFile, std::max<uint64_t>(4, T.nRec * 12), "the junction file");
+    R.alloc(R.dBlockSep, (blocks + 1) * 8, "the separator counts");
+    HIP_CHECK(hipHostMalloc((void**)&R.hState, LCB_JUNCTION_STATE_BYTES, hipHostMallocDefault));
+    HIP_CHECK(hipMemsetAsync(R.dState, 0, LCB_JUNCTION_STATE_BYTES, R.stream));
+    HIP_CHECK(hipMemsetAsync(R.dFlags, 0, 32, R.stream));
+
+    // ---- the file: read, copy, count
+    float ms = 0;
+    if (T.nRec)
+        for (uint8_t*& p : R.hStage) HIP_CHECK(hipHostMalloc((void**)&p, (size_t)T.tile * 12, hipHostMallocDefault));
+    HIP_CHECK(hipEventRecord(R.evA, R.stream));
+    for (uint64_t t = 0; t < T.tiles; t++) {
+        const int slot = (int)(t & 1);
+        if (t >= 2) HIP_CHECK(hipEventSynchronize(R.evCopy[slot]));
+        const double t0 = nowMs();
+        in.read(T, t, R.hStage[slot]);
+        S.read_ms += nowMs() - t0;
+        HIP_CHECK(hipMemcpyAsync(R.dFile + 3 * T.first(t), R.hStage[slot], T.count(t) * 12, hipMemcpyHostToDevice, R.stream));
+        HIP_CHECK(hipEventRecord(R.evCopy[slot], R.stream));
+        fileCount<<<T.bpt, F_T, 0, R.stream>>>(R.dFile, T.nRec, T.tile, t, R.dBlockSep + t * T.bpt, R.dFlags + 2);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(R.evB, R.stream));
+    HIP_CHECK(hipEventSynchronize(R.evB));
+    HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
+    S.upload_ms = ms;
+    S.tiles = (int64_t)T.tiles;
+    for (uint8_t*& p : R.hStage) if (p) { HIP_CHECK(hipHostFree(p)); p = nullptr; }
+
+    // ---- the raw records and the first raw index of every run
+    unsigned long long counts[2] = {0, 0};
+    HIP_CHECK(hipMemcpy(counts, R.dFlags + 2, 16, hipMemcpyDeviceToHost));
+    B.download_bytes += 16;
+    if (counts[0] > T.nRec) throw LcbError(std::string(FN) + ": internal error: more separators than records");
+    const uint64_t N = T.nRec - counts[0];
+    const size_t runs = (size_t)counts[0] + 1;
+    R.alloc(R.dRawPos, std::max<uint64_t>(1, N) * sizeof(uint32_t), "the raw positions");
+    R.alloc(R.dRawId, std::max<uint64_t>(1, N) * sizeof(int32_t), "the raw ids");
+    R.alloc(R.dRecFirst, (uint64_t)runs * 8, "the first raw index of every run");
+    HIP_CHECK(hipMemsetAsync(R.dRecFirst, 0xFF, (uint64_t)runs * 8, R.stream));
+    if (N)
+        R.timed(B.take_ms, [&]() {
+            lcb_graphk::graphScan<<<1, lcb_graphk::G_SCAN_T, 0, R.stream>>>(R.dBlockSep, blocks, R.dBlockSep + blocks);
+            fileTake<<<gridFor(blocks, 1, FN), F_T, 0, R.stream>>>(R.dFile, T.nRec, T.tile, T.bpt, R.dBlockSep, N, runs, R.dRawPos, R.dRawId, R.dRecFirst);
+        });
+    else HIP_CHECK(hipStreamSynchronize(R.stream));
+    R.release(R.dFile, std::max<uint64_t>(4, T.nRec * 12));
+    R.release(R.dBlockSep, (blocks + 1) * 8);
+    B.raw_occurrences = (int64_t)N;
+    g->nVertex = N ? (uint32_t)counts[1] : 0u;
+
+    // ---- the FASTA: parsed with the loader's parser, its code bytes and record bases go up
+    double t = nowMs();
+    const Source src = parseSource(FN, g, fasta, k, threads);
+    const size_t nRec = src.recLen.size();
+    R.alloc(R.dCodes, src.len, "the sequence");
+    R.alloc(R.dBase, (nRec + 1) * 8, "the record bases");
+    HIP_CHECK(hipEventRecord(R.evA, R.stream));
+    HIP_CHECK(hipMemsetAsync(R.dCodes, 4, src.len, R.stream));
+    HIP_CHECK(hipMemcpyAsync(R.dBase, src.base.data(), (nRec + 1) * 8, hipMemcpyHostToDevice, R.stream));
+    uploadCodes(R, g, src, threads);
+    HIP_CHECK(hipEventRecord(R.evB, R.stream));
+    HIP_CHECK(hipEventSynchronize(R.evB));
+    HIP_CHECK(hipEventElapsedTime(&ms, R.evA, R.evB));
+    S.upload_ms += ms;
+    B.parse_ms = nowMs() - t;
+    return graphTail(R, FN, g, N, runs, nRec, k, abundance, true, B, K);
+}
+
+// What produces the kept arrays in a run: one of the two front halves with its arguments bound.
+typedef std::function<uint64_t(Run&, lcb_graph*, lcb_graph_build_stats&, uint64_t&)> Front;
+
+// The graph as a host object: the kept arrays come down (10 bytes per kept occurrence), the device is released, the host patches the
+// letters the code bytes do not have and builds the CSR with the loader's code.
+lcb_graph* graphToHost(const char* const FN, const Front& front, int threads, lcb_graph_build_stats* stats)
+{
     if (threads < 1) threads = 1;
     lcb_graph_build_stats B;
     memset(&B, 0, sizeof(B));
@@ -675,7 +821,7 @@ lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, in
     uint64_t K = 0, patched = 0;
     {
         Run R;
-        patched = graphOnDevice(R, FN, g.get(), fasta, k, abundance, threads, ordinal, opts, B, K);
+        patched = front(R, g.get(), B, K);
 
         // ---- download: 10 bytes per kept occurrence
         const double td = nowMs();
@@ -706,14 +852,12 @@ lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, in
     return g.release();
 }
 
-// ---- FASTA -> graph + device in one call: the same device part; then the junction run is released except for the
-// four kept arrays, which travel in a holder to the device that is being created (device.hip: placement, the one download, the patch
-// of both copies, the table build with the host CSR taken from it).
-void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal, const lcb_junction_opts_ex& jopts,
-                         const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats)
+// Graph + device in one call: the junction run is released except for the four kept arrays, which travel in a holder to
+// the device that is being created (device.hip: placement, the one download, the patch of both copies, the table build with the host
+// CSR taken from it).
+void graphToDevice(const char* const FN, const Front& front, int threads, const lcb_params* p, int ordinal, const lcb_device_opts* dopts, lcb_graph** graph,
+                   lcb_device** device, lcb_open_stats* stats)
 {
-    const char* const FN = "lcb_open_fasta";
-    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load + lcb_device_create", ordinal);
     if (threads < 1) threads = 1;
     lcb_open_stats S;
     memset(&S, 0, sizeof(S));
@@ -724,7 +868,7 @@ void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abund
     uint64_t K = 0;
     {
         Run R;
-        ho.patched = graphOnDevice(R, FN, g.get(), fasta, k, abundance, threads, ordinal, jopts, B, K);
+        ho.patched = front(R, g.get(), B, K);
         // the holder takes the four arrays out of the run's account; everything else of the run goes with it (raw arrays, counters,
         // codes, record bases, stream and events)
         ho.kept.release = [](void* q) { return (int)hipFree(q); };
@@ -740,3 +884,49 @@ void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abund
     *graph = g.release();
     *device = d;
 }
+
+}  // namespace
+
+lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
+                                lcb_graph_build_stats* stats)
+{
+    const char* const FN = "lcb_graph_build";
+    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load", ordinal);
+    return graphToHost(FN, [&](Run& R, lcb_graph* g, lcb_graph_build_stats& B, uint64_t& K) {
+        return graphOnDevice(R, FN, g, fasta, k, abundance, std::max(1, threads), ordinal, opts, B, K);
+    }, threads, stats);
+}
+
+// ---- FASTA -> graph + device in one call
+void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal, const lcb_junction_opts_ex& jopts,
+                         const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats)
+{
+    const char* const FN = "lcb_open_fasta";
+    needDevice(FN, "the two-step route is lcb-mkgraph + lcb_graph_load + lcb_device_create", ordinal);
+    graphToDevice(FN, [&](Run& R, lcb_graph* g, lcb_graph_build_stats& B, uint64_t& K) {
+        return graphOnDevice(R, FN, g, fasta, k, abundance, std::max(1, threads), ordinal, jopts, B, K);
+    }, threads, p, ordinal, dopts, graph, device, stats);
+}
+
+// ---- junction file + FASTA -> the graph of lcb_graph_load, with the work on the device
+lcb_graph* lcb_graph_load_device_impl(const std::string& file, const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal,
+                                      const lcb_junction_opts_ex& opts, lcb_graph_build_stats* stats)
+{
+    const char* const FN = "lcb_graph_load_device";
+    needDevice(FN, "the CPU way is lcb_graph_load", ordinal);
+    return graphToHost(FN, [&](Run& R, lcb_graph* g, lcb_graph_build_stats& B, uint64_t& K) {
+        return graphFromFile(R, FN, g, file, fasta, k, abundance, std::max(1, threads), ordinal, opts, B, K);
+    }, threads, stats);
+}
+
+// ---- ... and graph + device in one call, the graph handed over in HBM
+void lcb_open_junctions_impl(const std::string& file, const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal,
+                             const lcb_junction_opts_ex& jopts, const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats)
+{
+    const char* const FN = "lcb_open_junctions";
+    needDevice(FN, "the CPU way is lcb_graph_load + lcb_device_create", ordinal);
+    graphToDevice(FN, [&](Run& R, lcb_graph* g, lcb_graph_build_stats& B, uint64_t& K) {
+        return graphFromFile(R, FN, g, file, fasta, k, abundance, std::max(1, threads), ordinal, jopts, B, K);
+    }, threads, p, ordinal, dopts, graph, device, stats);
+}
+

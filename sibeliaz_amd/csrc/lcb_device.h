@@ -153,6 +153,8 @@ struct LcbHandover {
 lcb_device* lcb_device_create_handover_impl(lcb_graph* g, const lcb_params* p, int ordinal, const lcb_device_opts* opts, LcbHandover& ho);
 void lcb_open_fasta_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal, const lcb_junction_opts_ex& jopts,
                          const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats);
+void lcb_open_junctions_impl(const std::string& file, const std::vector<std::string>& fasta, int k, int abundance, int threads, const lcb_params* p, int ordinal,
+                             const lcb_junction_opts_ex& jopts, const lcb_device_opts* dopts, lcb_graph** graph, lcb_device** device, lcb_open_stats* stats);
 
 // comm.hip — RCCL all-gather between the ranks of the round engine
 struct lcb_comm;

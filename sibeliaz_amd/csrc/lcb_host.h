@@ -45,6 +45,9 @@ void lcb_graph_build_csr(lcb_graph* g, int threads);
 // junctions.hip — the graph from the FASTA files alone, on one MI355X; arguments are already validated
 lcb_graph* lcb_graph_build_impl(const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal, const lcb_junction_opts_ex& opts,
                                 lcb_graph_build_stats* stats);
+// ... and from a junction file: the graph of lcb_graph_load_impl, read, filtered and compacted on the device
+lcb_graph* lcb_graph_load_device_impl(const std::string& file, const std::vector<std::string>& fasta, int k, int abundance, int threads, int ordinal,
+                                      const lcb_junction_opts_ex& opts, lcb_graph_build_stats* stats);
 // ... its patch of posCh: every sentinel byte the compaction left there (the next base is neither ACGT nor the end) gets the letter of
 // the graph's own string; -> the number found. patchQ / patchLetter (optional): the patched positions, ascending, and their letters
 uint64_t lcb_graph_patch_chars(lcb_graph* g, int threads, std::vector<uint64_t>* patchQ = nullptr, std::vector<uint8_t>* patchLetter = nullptr);

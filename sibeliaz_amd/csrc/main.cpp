@@ -9,7 +9,9 @@
 // default, or device) and the way to the graph (LCB_JUNCTIONS=file, the default: the junction file of --graph; or device: the
 // junctions come from the FASTA arguments on the GPU, --graph is still required by the parser but never opened) and the way the graph
 // reaches the device (LCB_HANDOVER=host, the default: the graph build releases the GPU and the device uploads its tables; or device,
-// which needs LCB_JUNCTIONS=device and one GPU: lcb_open_fasta, the graph's arrays stay in HBM and become the device's tables).
+// which needs LCB_JUNCTIONS=device and one GPU: lcb_open_fasta, the graph's arrays stay in HBM and become the device's tables) and the
+// place where the junction file is read (LCB_LOAD=host, the default: lcb_graph_load on host threads; or device, which needs
+// LCB_JUNCTIONS=file and one GPU: lcb_open_junctions, the file goes up as it is and graph and device come from one call).
 // The block finder itself runs on the MI355X through the C ABI in include/lcb.h.
 #include <cstdio>
 #include <cstdlib>
@@ -165,6 +167,29 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    // ... and where the junction file of --graph is read (LCB_LOAD=host, the default, or device: one call from the file to graph and device)
+    const char* loadEnv = getenv("LCB_LOAD");
+    const std::string loadRoute = loadEnv && *loadEnv ? loadEnv : "host";
+    if (loadRoute != "host" && loadRoute != "device") {
+        std::cerr << "error: LCB_LOAD is '" << loadRoute << "': it is host (the default) or device" << std::endl;
+        return 1;
+    }
+    const bool deviceLoad = loadRoute == "device";
+    if (deviceLoad) {
+        const char* gpus = getenv("LCB_GPUS");
+        if (deviceJunctions) {
+            std::cerr << "error: LCB_LOAD=device together with LCB_JUNCTIONS=device is not supported: there is no file to load (the junctions come from the FASTA files)" << std::endl;
+            return 1;
+        }
+        if (tablesEnv && *tablesEnv && !deviceTables) {
+            std::cerr << "error: LCB_LOAD=device together with LCB_TABLES=host is not supported: the tables of a graph opened on the device are built there (LCB_TABLES unset or device)" << std::endl;
+            return 1;
+        }
+        if (gpus && *gpus && atoi(gpus) > 1) {
+            std::cerr << "error: LCB_LOAD=device together with LCB_GPUS=" << gpus << " is not supported: the file is opened on the device of a single-GPU run (LCB_GPUS unset or 1)" << std::endl;
+            return 1;
+        }
+    }
     lcb_graph* g = nullptr;
     lcb_device* dev = nullptr;
     lcb_gpus* set = nullptr;
@@ -204,6 +229,19 @@ int main(int argc, char** argv)
                           << gs.peak_device_bytes << " parse_ms=" << gs.parse_ms << " upload_ms=" << gs.junctions.base.upload_ms << " insert_ms=" << gs.junctions.base.insert_ms
                           << " mark_ms=" << gs.junctions.mark_ms << " count_ms=" << gs.count_ms << " emit_ms=" << gs.junctions.base.emit_ms << " take_ms=" << gs.take_ms
                           << " abundance_ms=" << gs.abundance_ms << " compact_ms=" << gs.compact_ms << " download_ms=" << gs.download_ms << " csr_ms=" << gs.csr_ms << std::endl;
+        } else if (deviceLoad) {
+            // the junction file, opened on LCB_DEVICE: graph and device in one call, as with LCB_HANDOVER=device
+            const char* ordEnv = getenv("LCB_DEVICE");
+            lcb_open_stats os;
+            if (lcb_open_junctions(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t, &p, ordEnv && *ordEnv ? atoi(ordEnv) : 0, nullptr, nullptr, &g, &dev, &os) != LCB_OK) { fail(); break; }
+            if (getenv("LCB_VERBOSE"))
+                std::cerr << "lcb: load=device chromosomes=" << os.graph.junctions.base.records << " tiles=" << os.graph.junctions.base.tiles << " raw=" << os.graph.raw_occurrences
+                          << " kept=" << os.graph.kept_occurrences << " vertices=" << os.graph.vertices << " patched=" << os.graph.patched << " download_bytes=" << os.graph.download_bytes
+                          << " upload_bytes=" << os.tables.upload_bytes << " csr_download_bytes=" << os.csr_download_bytes << " peak_device_bytes=" << os.peak_device_bytes
+                          << " read_ms=" << os.graph.junctions.base.read_ms << " upload_ms=" << os.graph.junctions.base.upload_ms << " take_ms=" << os.graph.take_ms
+                          << " parse_ms=" << os.graph.parse_ms << " abundance_ms=" << os.graph.abundance_ms << " compact_ms=" << os.graph.compact_ms << " place_ms=" << os.place_ms
+                          << " download_ms=" << os.graph.download_ms << " patch_ms=" << os.patch_ms << " window_ms=" << os.tables.window_ms << " csr_ms=" << os.tables.csr_ms
+                          << " sort_ms=" << os.tables.sort_ms << " csr_download_ms=" << os.csr_download_ms << " gather_ms=" << os.tables.gather_ms << std::endl;
         } else
             g = lcb_graph_load(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t);
         if (!g) { fail(); break; }
