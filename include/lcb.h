@@ -265,6 +265,12 @@ lcb_device* lcb_device_create_ex(const lcb_graph* g, const lcb_params* p, int de
 /* Seeds handed to the compact / wide / big / huge kernel variant since the device was created (a seed that overflows
  * one variant is counted again in the next). */
 int lcb_device_mode_seeds(lcb_device* d, int64_t counts[4]);
+/* Why seeds climbed, since the device was created (read-only; a new function, no struct: LCB_ABI_VERSION is unchanged).
+ * counts[4 * v + j]: seeds that left variant v (compact / wide / big / huge) because j = 0 the instance pool, 1 the vote table,
+ * 2 the path set or 3 the result snapshot was full. info[0] = instance capacity of a huge slot now (it doubles when a seed outgrows
+ * it), info[1] = path set capacity of a compact slot now, info[2] = times the compact path set was enlarged, info[3] = times the
+ * result arena was enlarged because a launch filled it, info[4] = results remembered as too long for the wide variant's path set. */
+int lcb_device_overflows(lcb_device* d, int64_t counts[16], int64_t info[5]);
 /* hipEvent-timed kernel time (ms) and launches of the compact / wide / big / huge variant since the device was created, over all of its
  * streams (measurement: bench.py's roofline.per_kernel; the background batches of the side lanes count when they retire). */
 int lcb_device_mode_time(lcb_device* d, double ms[4], int64_t launches[4]);

@@ -152,7 +152,7 @@ _lib = None
 EXPORTS = [
     "lcb_last_error", "lcb_version", "lcb_abi_version", "lcb_graph_load", "lcb_graph_free", "lcb_graph_n_chr", "lcb_graph_n_pos", "lcb_graph_n_vertices",
     "lcb_graph_chr_len", "lcb_graph_chr_n_pos", "lcb_graph_chr_name", "lcb_graph_chr_start", "lcb_graph_pos_id", "lcb_graph_pos_pos",
-    "lcb_enumerate_seeds", "lcb_free", "lcb_device_create", "lcb_device_create_ex", "lcb_device_mode_seeds", "lcb_device_mode_time", "lcb_device_destroy", "lcb_device_reset_used", "lcb_device_mark_used",
+    "lcb_enumerate_seeds", "lcb_free", "lcb_device_create", "lcb_device_create_ex", "lcb_device_mode_seeds", "lcb_device_overflows", "lcb_device_mode_time", "lcb_device_destroy", "lcb_device_reset_used", "lcb_device_mark_used",
     "lcb_device_set_used", "lcb_device_set_stats_mode", "lcb_device_hbm_triad", "lcb_process_seeds", "lcb_process_seeds_fp", "lcb_device_kernel_time", "lcb_committer_create",
     "lcb_committer_free", "lcb_committer_commit_phase", "lcb_committer_take_marks", "lcb_committer_n_blocks", "lcb_committer_blocks",
     "lcb_committer_blocks_found", "lcb_committer_failures", "lcb_committer_used_words", "lcb_find_blocks", "lcb_find_blocks_ex",
@@ -218,6 +218,8 @@ def load_library():
     L.lcb_device_create_tables.argtypes = [vp, C.POINTER(Params), C.c_int, C.POINTER(DeviceOpts), C.c_int, C.POINTER(TableStats)]
     L.lcb_device_table_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_uint64]
     L.lcb_device_mode_seeds.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "lcb_device_overflows"):      # (an A/B library of an earlier round, LCB_LIB, lacks it)
+        L.lcb_device_overflows.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     if hasattr(L, "lcb_device_mode_time"):      # (an A/B library of an earlier round, LCB_LIB, lacks it)
         L.lcb_device_mode_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
     L.lcb_device_destroy.argtypes = [vp]
@@ -471,6 +473,19 @@ class Device:
         if self.L.lcb_device_mode_seeds(self.h, out):
             raise _err(self.L)
         return tuple(int(x) for x in out)
+
+    def overflows(self):
+        """Why seeds climbed since creation (lcb_device_overflows): {"counts": {variant: {"instances", "vote", "path", "snapshot"}} for the
+        compact / wide / big / huge variant, "huge_inst_cap", "compact_path_cap", "compact_path_grown", "arena_grown", "long_path_hints"}."""
+        if not hasattr(self.L, "lcb_device_overflows"):
+            raise LcbError("%s has no lcb_device_overflows: it was built before the accessor existed" % lib_path())
+        counts, info = (C.c_int64 * 16)(), (C.c_int64 * 5)()
+        if self.L.lcb_device_overflows(self.h, counts, info):
+            raise _err(self.L)
+        out = {"counts": {v: {w: int(counts[4 * i + j]) for j, w in enumerate(("instances", "vote", "path", "snapshot"))}
+                          for i, v in enumerate(("compact", "wide", "big", "huge"))}}
+        out.update(zip(("huge_inst_cap", "compact_path_cap", "compact_path_grown", "arena_grown", "long_path_hints"), (int(x) for x in info)))
+        return out
 
     def mode_time(self):
         """(ms, launches) of the (compact, wide, big, huge) kernel variants since creation: hipEvent-timed, all streams."""

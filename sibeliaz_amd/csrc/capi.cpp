@@ -322,6 +322,14 @@ int lcb_device_mode_seeds(lcb_device* d, int64_t counts[4])
     return LCB_OK;
     LCB_CATCH(LCB_ERR)
 }
+int lcb_device_overflows(lcb_device* d, int64_t counts[16], int64_t info[5])
+{
+    LCB_TRY
+    if (!d || !counts || !info) throw LcbError("lcb_device_overflows: null argument");
+    lcb_device_overflows_impl(d, counts, info);
+    return LCB_OK;
+    LCB_CATCH(LCB_ERR)
+}
 int lcb_device_mode_time(lcb_device* d, double ms[4], int64_t launches[4])
 {
     LCB_TRY

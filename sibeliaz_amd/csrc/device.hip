@@ -1164,6 +1164,13 @@ void lcb_device_kernel_time_impl(lcb_device* h, double* ms, int64_t* launches, d
 
 int64_t lcb_device_big_retries_impl(lcb_device* h) { return h->impl->bigRetries; }
 void lcb_device_mode_seeds_impl(lcb_device* h, int64_t out[4]) { for (int i = 0; i < 4; i++) out[i] = h->impl->modeSeeds[i]; }
+void lcb_device_overflows_impl(lcb_device* h, int64_t counts[16], int64_t info[5])
+{
+    const lcb_device_impl* d = h->impl;
+    static const int kStatus[4] = {LCB_ST_INST_OVF, LCB_ST_VOTE_OVF, LCB_ST_PATH_OVF, LCB_ST_BEST_OVF};
+    for (int m = 0; m < 4; m++) for (int j = 0; j < 4; j++) counts[4 * m + j] = d->overflow[m][kStatus[j]];
+    info[0] = d->ws[3].instCap; info[1] = d->ws[0].pathCap; info[2] = d->compactPathGrown; info[3] = d->arenaGrown; info[4] = d->longPathHints;
+}
 void lcb_device_mode_time_impl(lcb_device* h, double ms[4], int64_t launches[4])
 {
     // (the batches still on the lanes are accounted when they retire: a caller that wants a closed figure asks after a pass - the engine drains the lanes at its end)

@@ -128,15 +128,13 @@ struct Emu {
             // capacities as the product's device.hip chooses them per kernel variant (compact / wide / big / huge)
             W.pathCap = 65536; W.bodyCap = 32768;
             if (getenv("EMU_PATH_CAP")) { W.pathCap = (uint32_t)atoi(getenv("EMU_PATH_CAP")); W.bodyCap = W.pathCap / 2; }   // tiny path sets: long probe chains, colliding home slots
-            W.bestCap = mode == 0 ? LcbCfg<0>::IC : (mode == 1 ? LcbCfg<1>::IC : (mode == 2 ? LcbCfg<2>::IC : 8192));
-            W.instCap = mode == 2 ? LcbCfg<2>::IC : (mode == 3 ? 8192 : 0); W.voteCap = mode == 3 ? 65536 : 0;
+            // EMU_HUGE_CAP=n: the huge variant starts with n instances and a vote table of 8 n slots (a power of two), so that a small input reaches its growth
+            uint32_t hugeIC = 8192;
+            if (getenv("EMU_HUGE_CAP")) { hugeIC = (uint32_t)atoi(getenv("EMU_HUGE_CAP")); if (hugeIC < 64 || (hugeIC & (hugeIC - 1))) { fprintf(stderr, "emu: EMU_HUGE_CAP must be a power of two >= 64\n"); exit(2); } }
+            W.bestCap = mode == 0 ? LcbCfg<0>::IC : (mode == 1 ? LcbCfg<1>::IC : (mode == 2 ? LcbCfg<2>::IC : hugeIC));
+            W.instCap = mode == 2 ? LcbCfg<2>::IC : (mode == 3 ? hugeIC : 0); W.voteCap = mode == 3 ? 8 * hugeIC : 0;
             W.live = nullptr; W.nLive = nullptr; W.ctr = nullptr;
-            LcbSlotLayout L = lcb_slot_layout(W.pathCap, W.bodyCap, W.bestCap, W.instCap, W.voteCap);
-            c.slot.assign(L.total, 0);
-            int32_t* pk = (int32_t*)(c.slot.data() + L.pKeys);
-            for (uint32_t i = 0; i < W.pathCap; i++) pk[i] = LCB_EMPTY_KEY;
-            if (mode == 3) { int32_t* vk = (int32_t*)(c.slot.data() + L.vKey); for (uint32_t i = 0; i < W.voteCap; i++) vk[i] = LCB_EMPTY_KEY; }
-            W.base = c.slot.data(); W.slotBytes = L.total;
+            layoutSlot(c);
             W.dbg = nullptr; W.cursor = &c.cursor[0]; W.arenaCursor = (unsigned long long*)&c.cursor[2];
             c.arena.resize(1 << 18);
             c.fpArena.resize(1 << 18);
@@ -173,6 +171,54 @@ struct Emu {
         nViewsAlloc = nViews;
     }
 
+    // lays a context's workspace slot out for the capacities in its LcbWork and initialises it as the product's lcb_init_slots_kernel does (device.hip, allocWork)
+    void layoutSlot(EmuCtx& c)
+    {
+        LcbWork& W = c.W;
+        const LcbSlotLayout L = lcb_slot_layout(W.pathCap, W.bodyCap, W.bestCap, W.instCap, W.voteCap);
+        c.slot.assign(L.total, 0);
+        int32_t* pk = (int32_t*)(c.slot.data() + L.pKeys);
+        for (uint32_t i = 0; i < W.pathCap; i++) pk[i] = LCB_EMPTY_KEY;
+        if (W.voteCap) { int32_t* vk = (int32_t*)(c.slot.data() + L.vKey); for (uint32_t i = 0; i < W.voteCap; i++) vk[i] = LCB_EMPTY_KEY; }
+        W.base = c.slot.data(); W.slotBytes = L.total;
+    }
+    // A seed outgrew the huge variant: every capacity of its workspace doubles and the slots are laid out and initialised again, as
+    // runToCompletion does (device.hip). (The snapshot buffer doubles with the instance pool: it holds as many entries in every variant,
+    // so a seed never leaves a variant because of it before the pool is full.)
+    void growHuge()
+    {
+        if (ctx[0].W.instCap >= (1u << 20)) { fprintf(stderr, "FAIL: a seed needs more than 2^20 instances: the emulator's huge variant stops growing here\n"); exit(1); }
+        for (auto& c : ctx) {
+            LcbWork& W = c.W;
+            W.pathCap *= 2; W.bodyCap *= 2; W.instCap *= 2; W.voteCap *= 2; W.bestCap *= 2;
+            layoutSlot(c);
+        }
+        fprintf(stderr, "ladder: huge grown to %u\n", ctx[0].W.instCap);
+    }
+
+    // the wavefronts of a launch of this emulator: the case's EMU_NW; for the seeds that overflowed a smaller variant, with EMU_RETRY_NW=shipped, what the
+    // product launches this variant with (device.hip: LCB_NW_COMPACT 2, LCB_NW_WIDE 16, LCB_NW_BIG 16, LCB_NW_HUGE 8) where the flavour has that instantiation
+    static bool haveNw(int mode, int nw, bool ns)
+    {
+        return ns ? ((mode == 0 && (nw == 1 || nw == 2)) || (mode == 1 && (nw == 1 || nw == 16)) || (mode == 2 && (nw == 1 || nw == 8 || nw == 16)) || (mode == 3 && (nw == 1 || nw == 8)))
+                  : ((mode == 0 && (nw == 1 || nw == 4)) || (mode == 1 && (nw == 1 || nw == 8 || nw == 16)) || (mode == 2 && (nw == 1 || nw == 4)) || (mode == 3 && (nw == 1 || nw == 4)));
+    }
+
+    int launchNw() const
+    {
+        const char* nwEnv = getenv("EMU_NW");
+        int nw = nwEnv ? atoi(nwEnv) : 1;
+        // a seed that overflowed a smaller variant is re-run in THIS mode (runRetry) with the EMU_NW of the case: where this mode has no instantiation with that many
+        // wavefronts it runs with one (the fuzz campaign reached this with the small-pool compact variant, two wavefronts, and an overflow into the wide variant).
+        // EMU_RETRY_NW=shipped: with the product's wavefront count of this variant instead, where this flavour has it. The `ladder:` line names the count that ran.
+        const bool ns = getenv("EMU_NOSTATS") != nullptr;
+        static const int shippedNw[4] = {2, 16, 16, 8};
+        const char* rn = getenv("EMU_RETRY_NW");
+        if (isRetry && rn && !strcmp(rn, "shipped") && haveNw(mode, shippedNw[mode], ns)) nw = shippedNw[mode];
+        else if (!haveNw(mode, nw, ns) && isRetry) nw = 1;
+        return nw;
+    }
+
     void runCtx(EmuCtx& c)
     {
         LcbWork& W = c.W;
@@ -186,15 +232,7 @@ struct Emu {
         const LcbKSeed* sp = c.ks.data();
         const uint32_t n = (uint32_t)c.ks.size();
         if (!n) return;
-        const char* nwEnv = getenv("EMU_NW");
-        int nw = nwEnv ? atoi(nwEnv) : 1;
-        {   // a seed that overflowed a smaller variant is re-run in THIS mode (runRetry) with the EMU_NW of the case: where this mode has no instantiation with that many
-            // wavefronts it runs with one (the fuzz campaign reached this with the small-pool compact variant, two wavefronts, and an overflow into the wide variant)
-            const bool ns = getenv("EMU_NOSTATS") != nullptr;
-            const bool have = ns ? ((mode == 0 && (nw == 1 || nw == 2)) || (mode == 1 && (nw == 1 || nw == 16)) || (mode == 2 && (nw == 1 || nw == 8 || nw == 16)) || (mode == 3 && (nw == 1 || nw == 8)))
-                                 : ((mode == 0 && (nw == 1 || nw == 4)) || (mode == 1 && (nw == 1 || nw == 8 || nw == 16)) || (mode == 2 && (nw == 1 || nw == 4)) || (mode == 3 && (nw == 1 || nw == 4)));
-            if (!have && isRetry) nw = 1;
-        }
+        const int nw = launchNw();
         LcbSeedOut* op = c.out.data(); uint4* ar = c.arena.data(); LcbFpOut* fa = c.fpArena.data();
         const size_t arc = c.arena.size(), fac = c.fpArena.size();
         const bool noStats = getenv("EMU_NOSTATS") != nullptr;     // the shipped instantiation (checkpointed replay, no event counters)
@@ -277,21 +315,53 @@ struct Emu {
         firstPushes += out.empty() ? 0 : octr[0].c[pc];
         if (getenv("LCB_ENGINE_DEBUG_JOBS")) for (size_t i = 0; i < out.size(); i++) fprintf(stderr, "   done %zu pushes %llu inst %u\n", i, (unsigned long long)octr[i].c[pc], out[i].nInst);
     }
-    // Like the product's retry chain (device.hip): seeds that overflow the LDS capacities of this mode are run again in the next
-    // larger mode (small -> medium -> big), against the same `used` views.
+    // Like the product's retry chain (device.hip): seeds that overflow the capacities of this mode are run again in the next
+    // larger mode (compact -> wide -> big -> huge), against the same `used` views; seeds that overflow the huge mode are run in it
+    // again after its workspace has doubled (growHuge), as often as it takes.
     std::unique_ptr<Emu> next;
     bool isRetry = false;          // this emulator runs the seeds that overflowed a smaller variant
+    bool ladderLog = false;        // one `ladder:` line per variant visited (the per-seed modes: the tests of the capacity ladder parse them)
     void runRetry(const std::vector<LcbKSeed>& seeds)
     {
         run(seeds);
         std::vector<size_t> again;
-        for (size_t i = 0; i < out.size(); i++) if (out[i].status >= LCB_ST_INST_OVF && out[i].status <= LCB_ST_BEST_OVF) again.push_back(i);
-        if (again.empty() || mode >= 3) return;
-        if (!next) { next.reset(new Emu(g, p, mode + 1)); next->isRetry = true; }
-        next->used = used; next->T.used = next->used.data(); next->nViewsAlloc = nViewsAlloc;
-        next->viewTab = viewTab; next->T.viewTab = next->viewTab.data();
+        size_t by[5] = {0, 0, 0, 0, 0}, clash = 0;
+        const uint32_t poolCap = mode == 0 && getenv("EMU_COMPACT_SMALL") ? (uint32_t)LcbCfg<4>::IC : ctx[0].W.bestCap;
+        for (size_t i = 0; i < out.size(); i++) {
+            if (out[i].status >= LCB_ST_INST_OVF && out[i].status <= LCB_ST_BEST_OVF) again.push_back(i);
+            if (out[i].status <= LCB_ST_BEST_OVF) by[out[i].status]++;
+            // a full pool ends a seed within 64 instances of the capacity (one wavefront's worth is added at a time): an instance-pool status with fewer
+            // instances is the other way to it, the footprint slot that instances of two segments would have shared (lcb_push, segment-aware kernels only)
+            if (out[i].status == LCB_ST_INST_OVF && out[i].poolInst + 64 <= poolCap) clash++;
+        }
+        if (ladderLog) fprintf(stderr, "ladder: mode %d ok %zu inst %zu vote %zu path %zu best %zu clash %zu nw %d cap %u\n", mode, by[0], by[LCB_ST_INST_OVF], by[LCB_ST_VOTE_OVF],
+                               by[LCB_ST_PATH_OVF], by[LCB_ST_BEST_OVF], clash, launchNw(), poolCap);
+        if (again.empty()) return;
         std::vector<LcbKSeed> sub;
         for (size_t i : again) sub.push_back(seeds[i]);
+        if (mode >= 3) {
+            // the results so far are set aside, the overflowed seeds run through this emulator again, and their results take their places
+            std::vector<LcbSeedOut> out0; std::vector<LcbSeedCtr> octr0; std::vector<uint4> arena0; std::vector<LcbFpOut> fp0;
+            out0.swap(out); octr0.swap(octr); arena0.swap(arena); fp0.swap(fpArena);
+            growHuge();
+            runRetry(sub);
+            for (size_t k = 0; k < again.size(); k++) {
+                LcbSeedOut o = out[k];
+                if (o.status == 0) {
+                    const uint64_t ao = arena0.size(), fo = fp0.size();
+                    arena0.insert(arena0.end(), arena.begin() + o.arenaOff, arena.begin() + o.arenaOff + o.nInst);
+                    fp0.insert(fp0.end(), fpArena.begin() + o.fpOff, fpArena.begin() + o.fpOff + o.nFp);
+                    o.arenaOff = ao; o.fpOff = fo;
+                }
+                out0[again[k]] = o;
+                octr0[again[k]] = octr[k];
+            }
+            out.swap(out0); octr.swap(octr0); arena.swap(arena0); fpArena.swap(fp0);
+            return;
+        }
+        if (!next) { next.reset(new Emu(g, p, mode + 1)); next->isRetry = true; next->ladderLog = ladderLog; }
+        next->used = used; next->T.used = next->used.data(); next->nViewsAlloc = nViewsAlloc;
+        next->viewTab = viewTab; next->T.viewTab = next->viewTab.data();
         next->runRetry(sub);
         for (size_t k = 0; k < again.size(); k++) {
             LcbSeedOut o = next->out[k];
@@ -483,6 +553,7 @@ int main(int argc, char** argv)
             if (getenv("EMU_LIMIT") && (size_t)atoi(getenv("EMU_LIMIT")) < seeds.size()) seeds.resize((size_t)atoi(getenv("EMU_LIMIT")));   // the heavy seeds come first
             std::vector<LcbKSeed> ks;
             for (auto& s : seeds) ks.push_back(LcbKSeed{s.vid, s.ch, 0u, 0u});
+            emu.ladderLog = true;
             emu.runRetry(ks);
             std::vector<orc_inst> ref(1 << 16);
             for (size_t i = 0; i < seeds.size(); i++) {
