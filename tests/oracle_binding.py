@@ -117,5 +117,21 @@ class Oracle:
         words = np.packbits(bits[: (n_pos // 32 + 2) * 32].reshape(-1, 32)[:, ::-1], axis=1).view(">u4").astype("<u4").ravel()
         return words
 
+    def set_used(self, words, chr_start):
+        """Puts the oracle into the state of a flat `used` bitmap (uint32 words over g, the layout used_bitmap returns and
+        Device.set_used takes): 0 / 1 into the `used` byte of every position."""
+        n_pos = int(chr_start[-1])
+        w = np.ascontiguousarray(words, dtype="<u4")
+        if len(w) * 32 < n_pos:
+            raise ValueError("set_used: %d words for %d positions" % (len(w), n_pos))
+        bits = np.unpackbits(w.view(np.uint8), bitorder="little")
+        stride = self.L.orc_used_stride()
+        for c in range(self.L.orc_n_chr(self.h)):
+            n = self.L.orc_chr_n_pos(self.h, c)
+            if n == 0:
+                continue
+            raw = (C.c_uint8 * (n * stride)).from_address(self.L.orc_chr_used(self.h, c))
+            np.frombuffer(raw, dtype=np.uint8)[::stride][:n] = bits[int(chr_start[c]):int(chr_start[c]) + n]
+
     def reset_used(self):
         self.L.orc_reset_used(self.h)

@@ -21,10 +21,17 @@ def _setup(case, **device_opts):
 
 
 def _compare_all(case, st, dev, orc, seeds, what):
-    off, inst, score, _ = dev.process_seeds(seeds)
+    _compare_results(dev.process_seeds(seeds), seeds, [orc.process_seed(case.k, case.b, case.m, int(s["vid"]), int(s["ch"])) for s in seeds], what)
+
+
+def _compare_results(results, seeds, refs, what):
+    """The exact comparison of _compare_all for a caller that keeps the oracle's answers: results = dev.process_seeds(seeds),
+    refs[i] = orc.process_seed(...) of seeds[i] in the same `used` state."""
+    off, inst, score, _ = results
+    assert len(refs) == len(seeds) == len(score)
     bad = 0
     for i in range(len(seeds)):
-        ref, ref_score = orc.process_seed(case.k, case.b, case.m, int(seeds["vid"][i]), int(seeds["ch"][i]))
+        ref, ref_score = refs[i]
         got = inst[int(off[i]):int(off[i + 1])]
         tup = [(int(a["chr"]), int(a["front_idx"]), int(a["back_idx"]), int(a["positive"]) != 0) for a in got]
         if tup != ref or int(score[i]) != ref_score:
