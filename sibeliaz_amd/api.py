@@ -287,29 +287,68 @@ def _junction_opts(cls, opts, allowed):
     return o
 
 
+def _device_opts(mapping):
+    """A dict of lcb_device_opts fields (or None) -> DeviceOpts."""
+    o = DeviceOpts()
+    for name, v in (mapping or {}).items():
+        if not hasattr(o, name):
+            raise TypeError("unknown device option %r" % name)
+        setattr(o, name, int(v))
+    return o
+
+
+def _engine_hooks(hooks, engine):
+    """The engine knobs of a call (ENGINE_KNOBS) in its Hooks: the caller's, or those of one rank without callbacks."""
+    if hooks is None:
+        hooks = Hooks()
+        hooks.world = 1
+    for name, v in engine.items():
+        if name not in ENGINE_KNOBS:
+            raise TypeError("unknown engine knob %r" % name)
+        setattr(hooks, name, int(v))
+    return hooks
+
+
+def _paths(fasta_files):
+    """One path or a list of them, each a str, bytes or os.PathLike -> (array of char*, number of paths)."""
+    if isinstance(fasta_files, (str, bytes, os.PathLike)):
+        fasta_files = [fasta_files]
+    files = [os.fsencode(f) for f in fasta_files]
+    return (C.c_char_p * max(1, len(files)))(*files), len(files)
+
+
+def _as_dict(st, skip=()):
+    return {f: getattr(st, f) for f, _ in st._fields_ if f not in skip}
+
+
+def _junction_stats_dict(sx):
+    """JunctionStatsEx as a dict, its base part flattened into it."""
+    return dict(_as_dict(sx.base), **_as_dict(sx, ("base",)))
+
+
+def _graph_stats_dict(st):
+    """GraphBuildStats as a dict, its junction part flattened into it."""
+    return dict(_junction_stats_dict(st.junctions), **_as_dict(st, ("junctions",)))
+
+
 def build_junctions(fasta_files, k, out_file, device=0, partitions=None, mem_budget=None, **opts):
     """twopaco's role on one MI355X (lcb_junctions_build): FASTA files -> the junction file JunctionStorage reads, byte-identical to
     what the CPU tool `lcb-mkgraph` writes. opts: fields of lcb_junction_opts (table_log2, tile_windows). -> the stats as a dict.
     partitions (1..64, or 0 = as many as the budget asks for) and mem_budget (bytes of device memory, 0 = what is free) go through
     lcb_junctions_build_ex: the k-mer table is built in that many passes, the bytes stay the same, the dict gains the extended stats."""
     L = load_library()
-    if isinstance(fasta_files, (str, bytes, os.PathLike)):
-        fasta_files = [fasta_files]
-    files = [os.fsencode(f) for f in fasta_files]
-    arr = (C.c_char_p * max(1, len(files)))(*files)
+    arr, n = _paths(fasta_files)
     if partitions is None and mem_budget is None:
         o = _junction_opts(JunctionOpts, opts, ("abi", "table_log2", "tile_windows"))
         st = JunctionStats()
-        if L.lcb_junctions_build(arr, len(files), int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(st)):
+        if L.lcb_junctions_build(arr, n, int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(st)):
             raise _err(L)
-        return {f: getattr(st, f) for f, _ in JunctionStats._fields_}
+        return _as_dict(st)
     o = _junction_opts(JunctionOptsEx, dict(opts, partitions=partitions or 0, mem_budget=mem_budget or 0), ("abi", "table_log2", "tile_windows", "partitions", "mem_budget"))
     sx = JunctionStatsEx()
-    if L.lcb_junctions_build_ex(arr, len(files), int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(sx)):
+    if L.lcb_junctions_build_ex(arr, n, int(k), int(device), C.byref(o), os.fsencode(out_file), C.byref(sx)):
         raise _err(L)
-    out = {f: getattr(sx.base, f) for f, _ in JunctionStats._fields_}
-    out.update({f: getattr(sx, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
-    return out
+    return _junction_stats_dict(sx)
 
 
 def plan_junctions(windows, seq_bytes, budget, **opts):
@@ -329,13 +368,23 @@ class JunctionStorage:
 
     def __init__(self, graph_file, fasta_files, k, threads=1, abundance=150):
         self.L = load_library()
-        if isinstance(fasta_files, str):
-            fasta_files = [fasta_files]
-        arr = (C.c_char_p * len(fasta_files))(*[f.encode() for f in fasta_files])
-        self.h = self.L.lcb_graph_load(graph_file.encode(), arr, len(fasta_files), k, abundance, threads)
+        arr, n = _paths(fasta_files)
+        self.h = self.L.lcb_graph_load(graph_file.encode(), arr, n, k, abundance, threads)
         if not self.h:
             raise _err(self.L)
         self.k = k
+
+    @classmethod
+    def _made(cls, k, stats, call):
+        """The storage whose handle call(library, pointer to a GraphBuildStats) returns; with stats, and that struct as a dict."""
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.k = k
+        st = GraphBuildStats()
+        self.h = call(self.L, C.byref(st))
+        if not self.h:
+            raise _err(self.L)
+        return (self, _graph_stats_dict(st)) if stats else self
 
     @classmethod
     def build(cls, fasta_files, k, abundance=150, threads=1, device=0, partitions=None, mem_budget=None, stats=False, **opts):
@@ -345,23 +394,8 @@ class JunctionStorage:
         -> (storage, lcb_graph_build_stats as a dict, the junction part flattened into it). No CPU fallback."""
         o = _junction_opts(JunctionOptsEx, dict(opts, partitions=1 if partitions is None else partitions, mem_budget=mem_budget or 0),
                            ("abi", "table_log2", "tile_windows", "partitions", "mem_budget"))
-        if isinstance(fasta_files, (str, bytes, os.PathLike)):
-            fasta_files = [fasta_files]
-        files = [os.fsencode(f) for f in fasta_files]
-        arr = (C.c_char_p * max(1, len(files)))(*files)
-        self = cls.__new__(cls)
-        self.L = load_library()
-        self.k = k
-        st = GraphBuildStats()
-        self.h = self.L.lcb_graph_build(arr, len(files), int(k), int(abundance), int(threads), int(device), C.byref(o), C.byref(st))
-        if not self.h:
-            raise _err(self.L)
-        if not stats:
-            return self
-        out = {f: getattr(st.junctions.base, f) for f, _ in JunctionStats._fields_}
-        out.update({f: getattr(st.junctions, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
-        out.update({f: getattr(st, f) for f, _ in GraphBuildStats._fields_ if f != "junctions"})
-        return self, out
+        arr, n = _paths(fasta_files)
+        return cls._made(k, stats, lambda L, st: L.lcb_graph_build(arr, n, int(k), int(abundance), int(threads), int(device), C.byref(o), st))
 
     @classmethod
     def load_device(cls, junction_file, fasta_files, k, abundance=150, threads=1, device=0, mem_budget=None, stats=False, **opts):
@@ -370,23 +404,8 @@ class JunctionStorage:
         per upload tile); mem_budget as in build - the storage never depends on them. stats=True: -> (storage, lcb_graph_build_stats as a
         dict, flattened as build flattens it). No CPU fallback."""
         o = _junction_opts(JunctionOptsEx, dict(opts, mem_budget=mem_budget or 0), ("abi", "tile_windows", "mem_budget"))
-        if isinstance(fasta_files, (str, bytes, os.PathLike)):
-            fasta_files = [fasta_files]
-        files = [os.fsencode(f) for f in fasta_files]
-        arr = (C.c_char_p * max(1, len(files)))(*files)
-        self = cls.__new__(cls)
-        self.L = load_library()
-        self.k = k
-        st = GraphBuildStats()
-        self.h = self.L.lcb_graph_load_device(os.fsencode(junction_file), arr, len(files), int(k), int(abundance), int(threads), int(device), C.byref(o), C.byref(st))
-        if not self.h:
-            raise _err(self.L)
-        if not stats:
-            return self
-        out = {f: getattr(st.junctions.base, f) for f, _ in JunctionStats._fields_}
-        out.update({f: getattr(st.junctions, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
-        out.update({f: getattr(st, f) for f, _ in GraphBuildStats._fields_ if f != "junctions"})
-        return self, out
+        arr, n = _paths(fasta_files)
+        return cls._made(k, stats, lambda L, st: L.lcb_graph_load_device(os.fsencode(junction_file), arr, n, int(k), int(abundance), int(threads), int(device), C.byref(o), st))
 
     def close(self):
         if getattr(self, "h", None):
@@ -443,17 +462,13 @@ class Device:
         self.L = load_library()
         self.storage = storage
         self.params = params
-        o = DeviceOpts()
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError("unknown device option %r" % k)
-            setattr(o, k, int(v))
+        o = _device_opts(opts)
         st = TableStats()
         self.h = self.L.lcb_device_create_tables(storage.h, C.byref(params), ordinal, C.byref(o), TABLE_ROUTES[tables], C.byref(st))
         if not self.h:
             raise _err(self.L)
         self.tables = tables
-        self.table_stats = {f: getattr(st, f) for f, _ in TableStats._fields_}
+        self.table_stats = _as_dict(st)
 
     def read_table(self, name):
         """One table of the device as a numpy array (lcb_device_table_read; a test seam): pos_id, pos_pos, pos_win, pos_ch, pos_rev_ch by
@@ -527,7 +542,7 @@ class Device:
             raise _err(self.L)
         arr = _np_from(out.value, n, SEED_DTYPE)
         self.L.lcb_free(out)
-        return (arr, {f: getattr(st, f) for f, _ in SeedStats._fields_}) if stats else arr
+        return (arr, _as_dict(st)) if stats else arr
 
     def sort_seeds(self, seeds):
         """A copy of `seeds` in processing order (Bundle::operator<), sorted on the device; seeds with equal keys keep their order."""
@@ -597,20 +612,9 @@ def open_fasta(fasta_files, k, params, abundance=150, threads=1, device=0, parti
     "table_" in front where a name would repeat: table_vertices, table_upload_ms, table_csr_ms). One GPU, no CPU fallback."""
     o = _junction_opts(JunctionOptsEx, dict(junction_opts, partitions=1 if partitions is None else partitions, mem_budget=mem_budget or 0),
                        ("abi", "table_log2", "tile_windows", "partitions", "mem_budget"))
-    do = DeviceOpts()
-    for name, v in (device_opts or {}).items():
-        if not hasattr(do, name):
-            raise TypeError("unknown device option %r" % name)
-        setattr(do, name, int(v))
-    if isinstance(fasta_files, (str, bytes, os.PathLike)):
-        fasta_files = [fasta_files]
-    files = [os.fsencode(f) for f in fasta_files]
-    arr = (C.c_char_p * max(1, len(files)))(*files)
-    L = load_library()
-    g, d, st = C.c_void_p(), C.c_void_p(), OpenStats()
-    if L.lcb_open_fasta(arr, len(files), int(k), int(abundance), int(threads), C.byref(params), int(device), C.byref(o), C.byref(do), C.byref(g), C.byref(d), C.byref(st)):
-        raise _err(L)
-    return _opened(L, k, params, g, d, st, stats)
+    do = _device_opts(device_opts)
+    arr, n = _paths(fasta_files)
+    return _open(k, params, stats, lambda L, g, d, st: L.lcb_open_fasta(arr, n, int(k), int(abundance), int(threads), C.byref(params), int(device), C.byref(o), C.byref(do), g, d, st))
 
 
 def open_junctions(junction_file, fasta_files, k, params, abundance=150, threads=1, device=0, mem_budget=None, stats=False, device_opts=None, **junction_opts):
@@ -621,37 +625,29 @@ def open_junctions(junction_file, fasta_files, k, params, abundance=150, threads
     JunctionStorage.build; device_opts: a dict of lcb_device_opts fields. Close the device before the storage. stats=True: -> (storage,
     device, lcb_open_stats as a dict, flattened as open_fasta flattens it). One GPU, no CPU fallback."""
     o = _junction_opts(JunctionOptsEx, dict(junction_opts, mem_budget=mem_budget or 0), ("abi", "tile_windows", "mem_budget"))
-    do = DeviceOpts()
-    for name, v in (device_opts or {}).items():
-        if not hasattr(do, name):
-            raise TypeError("unknown device option %r" % name)
-        setattr(do, name, int(v))
-    if isinstance(fasta_files, (str, bytes, os.PathLike)):
-        fasta_files = [fasta_files]
-    files = [os.fsencode(f) for f in fasta_files]
-    arr = (C.c_char_p * max(1, len(files)))(*files)
+    do = _device_opts(device_opts)
+    arr, n = _paths(fasta_files)
+    return _open(k, params, stats, lambda L, g, d, st: L.lcb_open_junctions(os.fsencode(junction_file), arr, n, int(k), int(abundance), int(threads), C.byref(params), int(device),
+                                                                          C.byref(o), C.byref(do), g, d, st))
+
+
+def _open(k, params, stats, call):
+    """What open_fasta and open_junctions share: call(library, pointers to the graph handle, the device handle and an OpenStats) is
+    lcb_open_fasta / lcb_open_junctions; its handles and its lcb_open_stats come back as Python objects."""
     L = load_library()
     g, d, st = C.c_void_p(), C.c_void_p(), OpenStats()
-    if L.lcb_open_junctions(os.fsencode(junction_file), arr, len(files), int(k), int(abundance), int(threads), C.byref(params), int(device), C.byref(o), C.byref(do),
-                            C.byref(g), C.byref(d), C.byref(st)):
+    if call(L, C.byref(g), C.byref(d), C.byref(st)):
         raise _err(L)
-    return _opened(L, k, params, g, d, st, stats)
-
-
-def _opened(L, k, params, g, d, st, stats):
-    """The handles and the lcb_open_stats of lcb_open_fasta / lcb_open_junctions as Python objects."""
     storage = JunctionStorage.__new__(JunctionStorage)
     storage.L, storage.k, storage.h = L, k, g.value
     dev = Device.__new__(Device)
     dev.L, dev.storage, dev.params, dev.h, dev.tables = L, storage, params, d.value, "device"
-    dev.table_stats = {f: getattr(st.tables, f) for f, _ in TableStats._fields_}
+    dev.table_stats = _as_dict(st.tables)
     if not stats:
         return storage, dev
-    out = {f: getattr(st.graph.junctions.base, f) for f, _ in JunctionStats._fields_}
-    out.update({f: getattr(st.graph.junctions, f) for f, _ in JunctionStatsEx._fields_ if f != "base"})
-    out.update({f: getattr(st.graph, f) for f, _ in GraphBuildStats._fields_ if f != "junctions"})
-    out.update({("table_" + f if f in out else f): getattr(st.tables, f) for f, _ in TableStats._fields_})
-    out.update({f: getattr(st, f) for f, _ in OpenStats._fields_ if f not in ("graph", "tables")})
+    out = _graph_stats_dict(st.graph)
+    out.update({("table_" + f if f in out else f): v for f, v in dev.table_stats.items()})
+    out.update(_as_dict(st, ("graph", "tables")))
     return storage, dev, out
 
 
@@ -756,9 +752,7 @@ class GpuSet:
     def __init__(self, storage, params, ordinals, always_comm=False, **device_opts):
         self.L = load_library()
         self.params = params
-        o = DeviceOpts()
-        for k, v in device_opts.items():
-            setattr(o, k, int(v))
+        o = _device_opts(device_opts)
         ords = (C.c_int * len(ordinals))(*ordinals)
         self.h = self.L.lcb_gpus_create(storage.h, ords, len(ordinals), C.byref(params), C.byref(o), 1 if always_comm else 0)
         if not self.h:
@@ -783,47 +777,36 @@ class BlocksFinder:
         self.stats = None
         self.params = None
 
+    def _take_blocks(self, out, n, st):
+        """The blocks a call has returned in C memory become self.blocks (the memory is freed), its lcb_stats self.stats. -> the blocks"""
+        self.blocks = _np_from(out.value, n.value, BLOCK_DTYPE)
+        self.L.lcb_free(out)
+        self.stats = _as_dict(st)
+        return self.blocks
+
     def FindBlocksOnSet(self, gpus, seeds=None, threads=1, **engine):
         """One pass on a persistent GpuSet (tables resident, RCCL initialised): what bench.py --gpus N times."""
         self.params = gpus.params
-        hooks = Hooks()
-        hooks.world = 1
-        for k, v in engine.items():
-            if k not in ENGINE_KNOBS:
-                raise TypeError("unknown engine knob %r" % k)
-            setattr(hooks, k, int(v))
+        hooks = _engine_hooks(None, engine)
         s = self.storage.seeds(threads) if seeds is None else np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
         out, n, st = C.c_void_p(), C.c_int64(), Stats()
         if self.L.lcb_gpus_find_blocks(gpus.h, s.ctypes.data, len(s), C.byref(hooks), C.byref(out), C.byref(n), C.byref(st)):
             raise _err(self.L)
-        self.blocks = _np_from(out.value, n.value, BLOCK_DTYPE)
-        self.L.lcb_free(out)
-        self.stats = {f: getattr(st, f) for f, _ in Stats._fields_}
-        return self.blocks
+        return self._take_blocks(out, n, st)
 
     def FindBlocksGpus(self, minBlockSize, maxBranchSize, ordinals, seeds=None, threads=1, device_opts=None, **engine):
         """FindBlocks on several GPUs from this process (one host thread per GPU, RCCL all-gather between them)."""
         p = Params(self.k, minBlockSize, maxBranchSize, maxBranchSize, 8, 256)
         self.params = p
-        hooks = Hooks()
-        hooks.world = 1
-        for k, v in engine.items():
-            if k not in ENGINE_KNOBS:
-                raise TypeError("unknown engine knob %r" % k)
-            setattr(hooks, k, int(v))
-        o = DeviceOpts()
-        for k, v in (device_opts or {}).items():
-            setattr(o, k, int(v))
+        hooks = _engine_hooks(None, engine)
+        o = _device_opts(device_opts)
         s = self.storage.seeds(threads) if seeds is None else np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
         ords = (C.c_int * len(ordinals))(*ordinals)
         out, n, st = C.c_void_p(), C.c_int64(), Stats()
         if self.L.lcb_find_blocks_gpus(self.storage.h, ords, len(ordinals), C.byref(p), C.byref(o), s.ctypes.data, len(s), C.byref(hooks),
                                        C.byref(out), C.byref(n), C.byref(st)):
             raise _err(self.L)
-        self.blocks = _np_from(out.value, n.value, BLOCK_DTYPE)
-        self.L.lcb_free(out)
-        self.stats = {f: getattr(st, f) for f, _ in Stats._fields_}
-        return self.blocks
+        return self._take_blocks(out, n, st)
 
     def FindBlocks(self, minBlockSize, maxBranchSize, maxFlankingSize=None, lookingDepth=8, sampleSize=0, threads=1, device=None,
                    seeds=None, hooks=None, comm=None, **engine):
@@ -833,13 +816,7 @@ class BlocksFinder:
         if isinstance(seeds, str) and seeds != "device":
             raise ValueError("seeds=%r: None (host enumeration), \"device\" or an array of seeds" % (seeds,))
         if engine:
-            if hooks is None:
-                hooks = Hooks()
-                hooks.world = 1
-            for k, v in engine.items():
-                if k not in ENGINE_KNOBS:
-                    raise TypeError("unknown engine knob %r" % k)
-                setattr(hooks, k, int(v))
+            hooks = _engine_hooks(hooks, engine)
         p = Params(self.k, minBlockSize, maxBranchSize, maxBranchSize if maxFlankingSize is None else maxFlankingSize, lookingDepth, 256)
         self.params = p
         callback_engine = hooks is not None and bool(hooks.process)
@@ -861,13 +838,10 @@ class BlocksFinder:
                                                C.byref(hooks) if hooks is not None else None, C.byref(out), C.byref(n), C.byref(st))
             if rc:
                 raise _err(self.L)
-            self.blocks = _np_from(out.value, n.value, BLOCK_DTYPE)
-            self.L.lcb_free(out)
-            self.stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+            return self._take_blocks(out, n, st)
         finally:
             if own:
                 dev.close()
-        return self.blocks
 
     def GenerateOutput(self, outDir, genSeq=False, chunks=0, blocks=None, blocks_found=None):
         b = np.ascontiguousarray(self.blocks if blocks is None else blocks, dtype=BLOCK_DTYPE)

@@ -40,6 +40,51 @@ LcbEngineConfig tuningOf(const lcb_hooks* hooks)
     }
     return cfg;
 }
+
+// ---- the argument checks of the calls that open a graph or a device. Everything that can be refused without a device is refused
+// before one is looked for; an entry point is an ordered list of these calls, and the first fault wins, so the order is part of its
+// behaviour (it differs between the entry points). `fn`: the function the messages name.
+void needFasta(const std::string& fn, const char* const* fasta_files, int n_fasta)
+{
+    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
+}
+void needInputFiles(const std::string& fn, const char* junction_file, const char* const* fasta_files, int n_fasta)
+{
+    if (!junction_file || !fasta_files || n_fasta <= 0) throw LcbError(fn + ": missing input files");
+}
+// fn null: the loader's own check and words
+void checkK(const char* fn, int k)
+{
+    if (!fn) { if (k <= 0 || (k % 2) == 0) throw LcbError("value of K must be odd"); }
+    else if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(std::string(fn) + ": k must be odd and in 3..31, not " + std::to_string(k));
+}
+void mustOpen(const std::string& path, const std::string& message)
+{
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) throw LcbError(message);
+    fclose(f);
+}
+// The FASTA paths, none of them null. cannotOpen: empty = the files are not opened; else every file is, as its turn comes, and these
+// are the words in front of the path of one that cannot be.
+std::vector<std::string> fastaList(const std::string& fn, const char* const* fasta_files, int n_fasta, const std::string& cannotOpen = "")
+{
+    std::vector<std::string> fa;
+    for (int i = 0; i < n_fasta; i++) {
+        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
+        if (!cannotOpen.empty()) mustOpen(fasta_files[i], cannotOpen + fasta_files[i]);
+        fa.push_back(fasta_files[i]);
+    }
+    return fa;
+}
+lcb_junction_opts_ex junctionOptsOr(const lcb_junction_opts_ex* opts)
+{
+    if (opts) return *opts;
+    lcb_junction_opts_ex o;
+    memset(&o, 0, sizeof(o));
+    o.abi = LCB_ABI_VERSION;
+    return o;
+}
+
 int giveBlocks(std::vector<lcb_block>& v, lcb_block** blocks, int64_t* n_blocks)
 {
     *blocks = (lcb_block*)malloc((v.size() ? v.size() : 1) * sizeof(lcb_block));
@@ -62,8 +107,8 @@ void lcb_free(void* p) { free(p); }
 lcb_graph* lcb_graph_load(const char* junction_file, const char* const* fasta_files, int n_fasta, int k, int abundance, int threads)
 {
     LCB_TRY
-    if (!junction_file || !fasta_files || n_fasta <= 0) throw LcbError("lcb_graph_load: missing input files");
-    if (k <= 0 || (k % 2) == 0) throw LcbError("value of K must be odd");
+    needInputFiles("lcb_graph_load", junction_file, fasta_files, n_fasta);
+    checkK(nullptr, k);
     std::vector<std::string> fa(fasta_files, fasta_files + n_fasta);
     return lcb_graph_load_impl(junction_file, fa, k, abundance, threads);
     LCB_CATCH(nullptr)
@@ -79,7 +124,7 @@ const uint64_t* lcb_graph_chr_start(const lcb_graph* g) { return g->chrStart.dat
 const int32_t* lcb_graph_pos_id(const lcb_graph* g) { return g->posId.data(); }
 const uint32_t* lcb_graph_pos_pos(const lcb_graph* g) { return g->posPos.data(); }
 
-namespace {
+namespace {      // (inside extern "C", where these three have always been: the library exports their names)
 // `name`: the struct the messages name (lcb_junctions_build's options are checked after conversion).
 void checkJunctionOpts(const lcb_junction_opts_ex* opts, const std::string& name)
 {
@@ -91,23 +136,26 @@ void checkJunctionOpts(const lcb_junction_opts_ex* opts, const std::string& name
     if (opts->tile_windows > (1u << 30)) throw LcbError(name + ".tile_windows is " + std::to_string(opts->tile_windows) + ": at most 2^30");
 }
 
-// Everything that can be refused without a device is refused before the device is touched. `fn`: the function the messages name.
 void buildJunctions(const std::string& fn, const std::string& optsName, const char* const* fasta_files, int n_fasta, int k, int device_ordinal,
                     const lcb_junction_opts_ex& opts, const char* out_file, lcb_junction_stats_ex* stats)
 {
-    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(fn + ": k must be odd and in 3..31, not " + std::to_string(k));
-    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
+    checkK(fn.c_str(), k);
+    needFasta(fn, fasta_files, n_fasta);
     if (!out_file || !*out_file) throw LcbError(fn + ": no output file");
     checkJunctionOpts(&opts, optsName);
-    std::vector<std::string> fa;
-    for (int i = 0; i < n_fasta; i++) {
-        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
-        FILE* f = fopen(fasta_files[i], "rb");
-        if (!f) throw LcbError(fn + ": cannot open " + fasta_files[i]);
-        fclose(f);
-        fa.push_back(fasta_files[i]);
-    }
-    lcb_junctions_build_impl(fa, k, device_ordinal, opts, out_file, stats);
+    lcb_junctions_build_impl(fastaList(fn, fasta_files, n_fasta, fn + ": cannot open "), k, device_ordinal, opts, out_file, stats);
+}
+
+// The arguments of the two calls that open a junction file on the device, with the loader's words where the loader has them: the
+// junction file is opened before the FASTA files, and those only once none of their paths is null. fa: the FASTA paths.
+void fileArgs(const std::string& fn, const char* junction_file, const char* const* fasta_files, int n_fasta, int k, const lcb_junction_opts_ex* opts, std::vector<std::string>& fa)
+{
+    needInputFiles(fn, junction_file, fasta_files, n_fasta);
+    checkK(nullptr, k);
+    checkJunctionOpts(opts, "lcb_junction_opts_ex");
+    fa = fastaList(fn, fasta_files, n_fasta);
+    mustOpen(junction_file, "Can't read the input file");
+    for (const std::string& s : fa) mustOpen(s, "Can't open file " + s);
 }
 }  // namespace
 
@@ -115,9 +163,7 @@ int lcb_junctions_build(const char* const* fasta_files, int n_fasta, int k, int 
                         const char* out_file, lcb_junction_stats* stats)
 {
     LCB_TRY
-    lcb_junction_opts_ex o;
-    memset(&o, 0, sizeof(o));
-    o.abi = LCB_ABI_VERSION;
+    lcb_junction_opts_ex o = junctionOptsOr(nullptr);
     o.partitions = 1;       // the single-table path
     if (opts) { o.abi = opts->abi; o.table_log2 = opts->table_log2; o.tile_windows = opts->tile_windows; }
     lcb_junction_stats_ex x;
@@ -131,10 +177,7 @@ int lcb_junctions_build_ex(const char* const* fasta_files, int n_fasta, int k, i
                            const char* out_file, lcb_junction_stats_ex* stats)
 {
     LCB_TRY
-    lcb_junction_opts_ex o;
-    memset(&o, 0, sizeof(o));
-    o.abi = LCB_ABI_VERSION;
-    buildJunctions("lcb_junctions_build_ex", "lcb_junction_opts_ex", fasta_files, n_fasta, k, device_ordinal, opts ? *opts : o, out_file, stats);
+    buildJunctions("lcb_junctions_build_ex", "lcb_junction_opts_ex", fasta_files, n_fasta, k, device_ordinal, junctionOptsOr(opts), out_file, stats);
     return LCB_OK;
     LCB_CATCH(LCB_ERR)
 }
@@ -143,19 +186,12 @@ lcb_graph* lcb_graph_build(const char* const* fasta_files, int n_fasta, int k, i
                            lcb_graph_build_stats* stats)
 {
     LCB_TRY
-    const std::string fn = "lcb_graph_build";
-    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
-    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(fn + ": k must be odd and in 3..31, not " + std::to_string(k));
+    const char* fn = "lcb_graph_build";
+    needFasta(fn, fasta_files, n_fasta);
+    checkK(fn, k);
     checkJunctionOpts(opts, "lcb_junction_opts_ex");
-    std::vector<std::string> fa;
-    for (int i = 0; i < n_fasta; i++) {
-        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
-        fa.push_back(fasta_files[i]);
-    }
-    lcb_junction_opts_ex o;
-    memset(&o, 0, sizeof(o));
-    o.abi = LCB_ABI_VERSION;
-    return lcb_graph_build_impl(fa, k, abundance, threads, device_ordinal, opts ? *opts : o, stats);
+    const std::vector<std::string> fa = fastaList(fn, fasta_files, n_fasta);      // (not opened: the device is looked for first)
+    return lcb_graph_build_impl(fa, k, abundance, threads, device_ordinal, junctionOptsOr(opts), stats);
     LCB_CATCH(nullptr)
 }
 
@@ -165,51 +201,18 @@ int lcb_open_fasta(const char* const* fasta_files, int n_fasta, int k, int abund
     if (graph) *graph = nullptr;
     if (device) *device = nullptr;
     LCB_TRY
-    const std::string fn = "lcb_open_fasta";
-    if (!graph || !device || !p) throw LcbError(fn + ": null argument");
-    if (!fasta_files || n_fasta < 1) throw LcbError(fn + ": no FASTA file");
-    if (k < 3 || k > 31 || (k % 2) == 0) throw LcbError(fn + ": k must be odd and in 3..31, not " + std::to_string(k));
+    const char* fn = "lcb_open_fasta";
+    LCB_NEED(graph && device && p, fn);
+    needFasta(fn, fasta_files, n_fasta);
+    checkK(fn, k);
     checkJunctionOpts(jopts, "lcb_junction_opts_ex");
     checkAbi(nullptr, dopts);
-    if (p->max_branch >= 65000 || p->looking_depth >= 65000) throw LcbError("maxBranchSize / lookingDepth of 65000 or more are not supported by the device vote table");
-    std::vector<std::string> fa;
-    for (int i = 0; i < n_fasta; i++) {
-        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
-        FILE* f = fopen(fasta_files[i], "rb");         // (what the parser would say, said before a device is looked for)
-        if (!f) throw LcbError(std::string("Can't open file ") + fasta_files[i]);
-        fclose(f);
-        fa.push_back(fasta_files[i]);
-    }
-    lcb_junction_opts_ex o;
-    memset(&o, 0, sizeof(o));
-    o.abi = LCB_ABI_VERSION;
-    lcb_open_fasta_impl(fa, k, abundance, threads, p, device_ordinal, jopts ? *jopts : o, dopts, graph, device, stats);
+    paramsFitDevice(p);
+    const std::vector<std::string> fa = fastaList(fn, fasta_files, n_fasta, "Can't open file ");     // (what the parser would say, said before a device is looked for)
+    lcb_open_fasta_impl(fa, k, abundance, threads, p, device_ordinal, junctionOptsOr(jopts), dopts, graph, device, stats);
     return LCB_OK;
     LCB_CATCH(LCB_ERR)
 }
-
-namespace {
-// The arguments of the two calls that open a junction file on the device; what can be said without a device is said before one is
-// looked for, with the loader's words where the loader has them. fa: the FASTA paths.
-void fileArgs(const std::string& fn, const char* junction_file, const char* const* fasta_files, int n_fasta, int k, const lcb_junction_opts_ex* opts, std::vector<std::string>& fa)
-{
-    if (!junction_file || !fasta_files || n_fasta <= 0) throw LcbError(fn + ": missing input files");
-    if (k <= 0 || (k % 2) == 0) throw LcbError("value of K must be odd");
-    checkJunctionOpts(opts, "lcb_junction_opts_ex");
-    for (int i = 0; i < n_fasta; i++) {
-        if (!fasta_files[i]) throw LcbError(fn + ": FASTA path " + std::to_string(i) + " is null");
-        fa.push_back(fasta_files[i]);
-    }
-    FILE* f = fopen(junction_file, "rb");
-    if (!f) throw LcbError("Can't read the input file");
-    fclose(f);
-    for (const std::string& s : fa) {
-        f = fopen(s.c_str(), "rb");
-        if (!f) throw LcbError("Can't open file " + s);
-        fclose(f);
-    }
-}
-}  // namespace
 
 lcb_graph* lcb_graph_load_device(const char* junction_file, const char* const* fasta_files, int n_fasta, int k, int abundance, int threads, int device_ordinal,
                                  const lcb_junction_opts_ex* opts, lcb_graph_build_stats* stats)
@@ -217,10 +220,7 @@ lcb_graph* lcb_graph_load_device(const char* junction_file, const char* const* f
     LCB_TRY
     std::vector<std::string> fa;
     fileArgs("lcb_graph_load_device", junction_file, fasta_files, n_fasta, k, opts, fa);
-    lcb_junction_opts_ex o;
-    memset(&o, 0, sizeof(o));
-    o.abi = LCB_ABI_VERSION;
-    return lcb_graph_load_device_impl(junction_file, fa, k, abundance, threads, device_ordinal, opts ? *opts : o, stats);
+    return lcb_graph_load_device_impl(junction_file, fa, k, abundance, threads, device_ordinal, junctionOptsOr(opts), stats);
     LCB_CATCH(nullptr)
 }
 
@@ -230,16 +230,13 @@ int lcb_open_junctions(const char* junction_file, const char* const* fasta_files
     if (graph) *graph = nullptr;
     if (device) *device = nullptr;
     LCB_TRY
-    const std::string fn = "lcb_open_junctions";
-    if (!graph || !device || !p) throw LcbError(fn + ": null argument");
+    const char* fn = "lcb_open_junctions";
+    LCB_NEED(graph && device && p, fn);
     checkAbi(nullptr, dopts);
-    if (p->max_branch >= 65000 || p->looking_depth >= 65000) throw LcbError("maxBranchSize / lookingDepth of 65000 or more are not supported by the device vote table");
+    paramsFitDevice(p);
     std::vector<std::string> fa;
     fileArgs(fn, junction_file, fasta_files, n_fasta, k, jopts, fa);
-    lcb_junction_opts_ex o;
-    memset(&o, 0, sizeof(o));
-    o.abi = LCB_ABI_VERSION;
-    lcb_open_junctions_impl(junction_file, fa, k, abundance, threads, p, device_ordinal, jopts ? *jopts : o, dopts, graph, device, stats);
+    lcb_open_junctions_impl(junction_file, fa, k, abundance, threads, p, device_ordinal, junctionOptsOr(jopts), dopts, graph, device, stats);
     return LCB_OK;
     LCB_CATCH(LCB_ERR)
 }
@@ -453,14 +450,10 @@ int lcb_find_blocks_ex(const lcb_graph* g, lcb_device* d, const lcb_params* p, c
 {
     LCB_TRY
     LCB_NEED(g && p && (seeds || n_seeds == 0) && blocks && n_blocks, "lcb_find_blocks_ex");
-    LcbEngineConfig cfg;
-    checkAbi(hooks, nullptr);
+    LcbEngineConfig cfg = tuningOf(hooks);
     if (hooks) {
         cfg.rank = hooks->rank; cfg.world = hooks->world > 0 ? hooks->world : 1;
         cfg.allgather = hooks->allgather; cfg.allgatherUser = hooks->allgather_user;
-        cfg.roundPhases = hooks->round_phases; cfg.progress = hooks->progress != 0;
-        cfg.roundFixed = hooks->round_fixed != 0; cfg.eagerPhases = hooks->eager_phases; cfg.maxViews = hooks->max_views;
-        cfg.maxJobs = hooks->max_jobs; cfg.predictF = hooks->predict_f; cfg.exchangeAlways = hooks->exchange_always != 0; cfg.countEvents = hooks->count_events != 0; cfg.syncJobs = hooks->sync_jobs != 0; cfg.lazySpan = hooks->lazy_span; cfg.sparseRounds = hooks->sparse_rounds;
     }
     std::vector<lcb_block> v;
     if (d) lcb_find_blocks_impl(g, d, p, seeds, n_seeds, cfg, v, stats);
@@ -471,20 +464,10 @@ int lcb_find_blocks_ex(const lcb_graph* g, lcb_device* d, const lcb_params* p, c
         lcb_engine_run(g, p, seeds, n_seeds, proc, cfg, v, &es);
         if (stats) {
             memset(stats, 0, sizeof(*stats));
-            stats->seeds = n_seeds; stats->blocks_found = es.blocksFound; stats->failures = es.failures; stats->wall_ms = es.wallMs;
-            stats->rounds = es.rounds; stats->recompute_launches = es.recomputeLaunches; stats->recomputed_seeds = es.recomputedSeeds;
-            stats->conflict_launches = es.conflictLaunches; stats->conflict_seeds = es.conflictSeeds; stats->exchanges = es.exchanges;
-            stats->jobs_used = es.jobsUsed; stats->views_built = es.viewsBuilt; stats->over_predicted = es.overPredicted;
-            stats->process_ms = es.processMs; stats->plan_ms = es.planMs; stats->events = es.events;
-            stats->side_batches = es.sideBatches; stats->side_jobs = es.sideJobs; stats->side_taken = es.sideTaken; stats->side_void = es.sideVoid; stats->side_failed = es.sideFailed;
-            stats->early_critical = es.earlyCritical; stats->lazy_seeds = es.lazySeeds; stats->host_dead = es.hostDead; stats->collectives = es.collectives;
+            lcb_stats_from_engine(es, n_seeds, stats);
         }
     }
-    *blocks = (lcb_block*)malloc((v.size() ? v.size() : 1) * sizeof(lcb_block));
-    if (!*blocks) throw LcbError("out of memory");
-    if (!v.empty()) memcpy(*blocks, v.data(), v.size() * sizeof(lcb_block));
-    *n_blocks = (int64_t)v.size();
-    return LCB_OK;
+    return giveBlocks(v, blocks, n_blocks);
     LCB_CATCH(LCB_ERR)
 }
 
@@ -497,11 +480,7 @@ int lcb_find_blocks(const lcb_graph* g, lcb_device* d, const lcb_params* p, cons
     LcbEngineConfig cfg;
     cfg.progress = progress != 0;
     lcb_find_blocks_impl(g, d, p, seeds, n_seeds, cfg, v, stats);
-    *blocks = (lcb_block*)malloc((v.size() ? v.size() : 1) * sizeof(lcb_block));
-    if (!*blocks) throw LcbError("out of memory");
-    if (!v.empty()) memcpy(*blocks, v.data(), v.size() * sizeof(lcb_block));
-    *n_blocks = (int64_t)v.size();
-    return LCB_OK;
+    return giveBlocks(v, blocks, n_blocks);
     LCB_CATCH(LCB_ERR)
 }
 

@@ -547,6 +547,35 @@ void createOptions(lcb_device_impl* d, uint32_t nCu)
     createPools(d, nCu);
 }
 
+// chrLoHi and segBase: the two small tables every route uploads first
+void uploadSmallTables(lcb_device_impl* d)
+{
+    const LcbSegPlan& plan = d->plan;
+    std::vector<uint2> lh(d->g->nChr());
+    for (size_t c = 0; c < lh.size(); c++) lh[c] = uint2{plan.chrLo[c], plan.chrHi[c]};
+    d->T.chrLoHi = d->upload(lh.data(), lh.size());
+    d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
+}
+
+// The table build on the device (tables.hip), from the per-position arrays in d->T: posWin and occStart are allocated here, occRec by the
+// build. hand: the hand-over route's extras (null on the device route).
+void buildTablesOnDevice(lcb_device_impl* d, const char* fn, LcbTableHandover* hand)
+{
+    const uint64_t D = d->plan.devPositions ? d->plan.devPositions : 1, V1 = (uint64_t)d->g->nVertex + 1;
+    uint32_t* win = d->devAlloc<uint32_t>((size_t)D * sizeof(uint32_t));
+    d->T.posWin = win;
+    LcbTableJob job;
+    job.fn = fn; job.stream = (void*)d->stream; job.g = d->g; job.plan = &d->plan; job.seg = d->seg; job.maxBranch = (uint32_t)d->p.max_branch;
+    job.posId = d->T.posId; job.posPos = d->T.posPos; job.segBase = d->T.segBase; job.posWin = win; job.hand = hand;
+    if (d->seg) { uint64_t* os = d->devAlloc<uint64_t>((size_t)V1 * 8); d->T.occStart64 = os; d->T.occStart32 = nullptr; job.occStart = os; }
+    else { uint32_t* os = d->devAlloc<uint32_t>((size_t)V1 * 4); d->T.occStart32 = os; d->T.occStart64 = nullptr; job.occStart = os; }
+    job.owner = d;
+    job.alloc = [](void* o, size_t bytes) { return (void*)((lcb_device_impl*)o)->devAlloc<uint8_t>(bytes); };
+    job.drop = [](void* o, void* p) { uint8_t* q = (uint8_t*)p; ((lcb_device_impl*)o)->drop(q); };
+    lcb_build_tables_impl(job, d->tableStats);
+    d->T.occRec = (const uint4*)job.occRec;
+}
+
 // The device route of the tables (LCB_TABLES_DEVICE; tables.hip): only the four per-position arrays go up; posWin,
 // occStart and occRec - functions of them - are computed there. The host's `win` and `rec` vectors are never built.
 void createTablesOnDevice(lcb_device_impl* d)
@@ -560,18 +589,7 @@ void createTablesOnDevice(lcb_device_impl* d)
     d->T.posPos = d->uploadSeg(g->posPos.data(), plan);
     d->T.posCh = d->uploadSeg(g->posCh.data(), plan);
     d->T.posRevCh = d->uploadSeg(g->posRevCh.data(), plan);
-    uint32_t* win = d->devAlloc<uint32_t>((size_t)D * sizeof(uint32_t));
-    d->T.posWin = win;
-    LcbTableJob job;
-    job.fn = fn; job.stream = (void*)d->stream; job.g = g; job.plan = &plan; job.seg = d->seg; job.maxBranch = (uint32_t)d->p.max_branch;
-    job.posId = d->T.posId; job.posPos = d->T.posPos; job.segBase = d->T.segBase; job.posWin = win;
-    if (d->seg) { uint64_t* os = d->devAlloc<uint64_t>((size_t)V1 * 8); d->T.occStart64 = os; d->T.occStart32 = nullptr; job.occStart = os; }
-    else { uint32_t* os = d->devAlloc<uint32_t>((size_t)V1 * 4); d->T.occStart32 = os; d->T.occStart64 = nullptr; job.occStart = os; }
-    job.owner = d;
-    job.alloc = [](void* o, size_t bytes) { return (void*)((lcb_device_impl*)o)->devAlloc<uint8_t>(bytes); };
-    job.drop = [](void* o, void* p) { uint8_t* q = (uint8_t*)p; ((lcb_device_impl*)o)->drop(q); };
-    lcb_build_tables_impl(job, d->tableStats);
-    d->T.occRec = (const uint4*)job.occRec;
+    buildTablesOnDevice(d, fn, nullptr);
 }
 
 // The tables on the hand-over route (lcb_open_fasta): the four per-position arrays are already in HBM, left there by the
@@ -587,12 +605,7 @@ void createTablesHandover(lcb_device_impl* d, lcb_graph* g, LcbHandover& ho)
     const LcbSegPlan& plan = d->plan;
     const uint64_t K = g->nPos(), D = plan.devPositions ? plan.devPositions : 1, V1 = (uint64_t)g->nVertex + 1, qBytes = d->seg ? 8 : 4;
     if (kept.K != K) throw LcbError(std::string(fn) + ": internal error: the holder has " + std::to_string(kept.K) + " positions, the graph " + std::to_string(K));
-    {
-        std::vector<uint2> lh(g->nChr());
-        for (size_t c = 0; c < lh.size(); c++) lh[c] = uint2{plan.chrLo[c], plan.chrHi[c]};
-        d->T.chrLoHi = d->upload(lh.data(), lh.size());
-        d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
-    }
+    uploadSmallTables(d);
     const uint64_t small = (uint64_t)g->nChr() * 8 + plan.segDev.size() * 8, dense = 10 * std::max<uint64_t>(1, K);
     int32_t* posId = nullptr;
     uint32_t* posPos = nullptr;
@@ -656,20 +669,9 @@ void createTablesHandover(lcb_device_impl* d, lcb_graph* g, LcbHandover& ho)
     S.graph.download_ms += nowMs() - t0;
 
     // ---- the table build, with the CSR taken from it
-    uint32_t* win = d->devAlloc<uint32_t>((size_t)D * sizeof(uint32_t));
-    d->T.posWin = win;
     LcbTableHandover hand;
     hand.g = g; hand.posCh = posCh; hand.patchQ = patchQ.data(); hand.patchLetter = patchLetter.data(); hand.nPatch = (uint64_t)patchQ.size();
-    LcbTableJob job;
-    job.fn = fn; job.stream = (void*)d->stream; job.g = g; job.plan = &plan; job.seg = d->seg; job.maxBranch = (uint32_t)d->p.max_branch;
-    job.posId = posId; job.posPos = posPos; job.segBase = d->T.segBase; job.posWin = win; job.hand = &hand;
-    if (d->seg) { uint64_t* os = d->devAlloc<uint64_t>((size_t)V1 * 8); d->T.occStart64 = os; d->T.occStart32 = nullptr; job.occStart = os; }
-    else { uint32_t* os = d->devAlloc<uint32_t>((size_t)V1 * 4); d->T.occStart32 = os; d->T.occStart64 = nullptr; job.occStart = os; }
-    job.owner = d;
-    job.alloc = [](void* o, size_t bytes) { return (void*)((lcb_device_impl*)o)->devAlloc<uint8_t>(bytes); };
-    job.drop = [](void* o, void* p) { uint8_t* q = (uint8_t*)p; ((lcb_device_impl*)o)->drop(q); };
-    lcb_build_tables_impl(job, d->tableStats);
-    d->T.occRec = (const uint4*)job.occRec;
+    buildTablesOnDevice(d, fn, &hand);
     S.patch_ms = hand.patchMs; S.csr_download_ms = hand.csrMs; S.csr_download_bytes = hand.csrBytes;
     S.peak_device_bytes = std::max(std::max(ho.junctionPeak, placePeak), resident + D * 4 + V1 * qBytes + hand.peakBytes);
 }
@@ -680,12 +682,7 @@ void createTables(lcb_device_impl* d)
     const lcb_graph* g = d->g;
     const LcbSegPlan& plan = d->plan;
     const uint64_t nOcc = g->nPos();
-    {
-        std::vector<uint2> lh(g->nChr());
-        for (size_t c = 0; c < lh.size(); c++) lh[c] = uint2{plan.chrLo[c], plan.chrHi[c]};
-        d->T.chrLoHi = d->upload(lh.data(), lh.size());
-        d->T.segBase = d->upload(plan.segDev.data(), plan.segDev.size());
-    }
+    uploadSmallTables(d);
     if (d->tables == LCB_TABLES_DEVICE) { createTablesOnDevice(d); return; }
     d->T.posId = d->uploadSeg(g->posId.data(), plan);
     d->T.posPos = d->uploadSeg(g->posPos.data(), plan);
@@ -841,7 +838,7 @@ static lcb_device* createDevice(const lcb_graph* g, const lcb_params* p, int ord
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         throw LcbError("no HIP device available: the block-finder hot path runs only on the GPU (there is no CPU fallback)");
     if (ordinal < 0 || ordinal >= count) throw LcbError("HIP device ordinal out of range");
-    if (p->max_branch >= 65000 || p->looking_depth >= 65000) throw LcbError("maxBranchSize / lookingDepth of 65000 or more are not supported by the device vote table");
+    paramsFitDevice(p);
     auto* d = new lcb_device_impl();
     auto* handle = new lcb_device{d};
     try {
@@ -1696,16 +1693,8 @@ void lcb_find_blocks_impl(const lcb_graph* g, lcb_device* dev, const lcb_params*
     if (stats) {
         double ms = 0, busy = 0, side = 0; int64_t l = 0;
         lcb_device_kernel_time_impl(dev, &ms, &l, &busy, &side);
+        lcb_stats_from_engine(es, nSeeds, stats);
         stats->kernel_busy_ms = busy; stats->kernel_side_ms = side;
-        stats->seeds = nSeeds; stats->blocks_found = es.blocksFound; stats->failures = es.failures;
         stats->launches = l; stats->kernel_ms = ms; stats->big_retries = lcb_device_big_retries_impl(dev) - retries0;
-        stats->wall_ms = es.wallMs;
-        stats->rounds = es.rounds; stats->recompute_launches = es.recomputeLaunches; stats->recomputed_seeds = es.recomputedSeeds;
-        stats->conflict_launches = es.conflictLaunches; stats->conflict_seeds = es.conflictSeeds; stats->exchanges = es.exchanges;
-        stats->jobs_used = es.jobsUsed; stats->views_built = es.viewsBuilt; stats->over_predicted = es.overPredicted;
-        stats->process_ms = es.processMs; stats->plan_ms = es.planMs; stats->events = es.events;
-        stats->side_batches = es.sideBatches; stats->side_jobs = es.sideJobs; stats->side_taken = es.sideTaken; stats->side_void = es.sideVoid; stats->side_failed = es.sideFailed;
-        stats->early_critical = es.earlyCritical;
-        stats->lazy_seeds = es.lazySeeds; stats->host_dead = es.hostDead; stats->collectives = es.collectives;
     }
 }

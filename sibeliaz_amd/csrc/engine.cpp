@@ -1031,3 +1031,21 @@ void lcb_engine_run(const lcb_graph* g, const lcb_params* p, const lcb_seed* see
     st.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
 }
+
+// The engine's part of lcb_stats: every field but the five of the device's kernels (launches, big_retries, kernel_ms, kernel_busy_ms,
+// kernel_side_ms), which stay as the caller has set them.
+void lcb_stats_from_engine(const LcbEngineStats& es, int64_t nSeeds, lcb_stats* stats)
+{
+    stats->seeds = nSeeds; stats->blocks_found = es.blocksFound; stats->failures = es.failures; stats->wall_ms = es.wallMs;
+    stats->rounds = es.rounds; stats->recompute_launches = es.recomputeLaunches; stats->recomputed_seeds = es.recomputedSeeds;
+    stats->conflict_launches = es.conflictLaunches; stats->conflict_seeds = es.conflictSeeds; stats->exchanges = es.exchanges;
+    stats->jobs_used = es.jobsUsed; stats->views_built = es.viewsBuilt; stats->over_predicted = es.overPredicted;
+    stats->process_ms = es.processMs; stats->plan_ms = es.planMs; stats->events = es.events;
+    stats->side_batches = es.sideBatches; stats->side_jobs = es.sideJobs; stats->side_taken = es.sideTaken; stats->side_void = es.sideVoid; stats->side_failed = es.sideFailed;
+    stats->early_critical = es.earlyCritical; stats->lazy_seeds = es.lazySeeds; stats->host_dead = es.hostDead; stats->collectives = es.collectives;
+}
+
+void paramsFitDevice(const lcb_params* p)
+{
+    if (p->max_branch >= 65000 || p->looking_depth >= 65000) throw LcbError("maxBranchSize / lookingDepth of 65000 or more are not supported by the device vote table");
+}

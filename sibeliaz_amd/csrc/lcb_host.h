@@ -246,5 +246,9 @@ struct LcbEngineStats {
 
 void lcb_engine_run(const lcb_graph* g, const lcb_params* p, const lcb_seed* seeds, int64_t nSeeds, LcbProcessor& proc,
                     const LcbEngineConfig& cfg, std::vector<lcb_block>& blocks, LcbEngineStats* stats);
+// the engine's part of lcb_stats; the five fields of the device's kernels are the caller's (zeroed, or filled by lcb_find_blocks_impl)
+void lcb_stats_from_engine(const LcbEngineStats& es, int64_t nSeeds, lcb_stats* stats);
+// throws for a maxBranchSize / lookingDepth the device's vote table cannot hold: before a device is looked for, and when one is made
+void paramsFitDevice(const lcb_params* p);
 
 #endif

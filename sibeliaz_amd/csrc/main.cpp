@@ -3,21 +3,25 @@
 // Same flags, defaults, stdout banners, output files and exit codes, so line 146 of the reference's
 // `sibeliaz` wrapper script keeps working verbatim:
 //   sibeliaz-lcb --graph <junctions> <fasta...> -k <odd> -b <int> -o <dir> -m <int> -t <int> --abundance <int> [--noseq] --chunks <int>
-// `-t` stays "host threads" (loading, seed enumeration); the GPU is chosen by the environment
-// (LCB_DEVICE, default 0; HIP_VISIBLE_DEVICES also applies), never by a new flag, and so are the place where the seeds are
-// enumerated (LCB_SEEDS=host, the default, or device), the place where the device's tables are computed (LCB_TABLES=host, the
-// default, or device) and the way to the graph (LCB_JUNCTIONS=file, the default: the junction file of --graph; or device: the
-// junctions come from the FASTA arguments on the GPU, --graph is still required by the parser but never opened) and the way the graph
-// reaches the device (LCB_HANDOVER=host, the default: the graph build releases the GPU and the device uploads its tables; or device,
-// which needs LCB_JUNCTIONS=device and one GPU: lcb_open_fasta, the graph's arrays stay in HBM and become the device's tables) and the
-// place where the junction file is read (LCB_LOAD=host, the default: lcb_graph_load on host threads; or device, which needs
-// LCB_JUNCTIONS=file and one GPU: lcb_open_junctions, the file goes up as it is and graph and device come from one call).
+// `-t` stays "host threads" (loading, seed enumeration). Everything else is chosen by the environment, never by a new flag; unset and
+// empty mean the default, any other spelling and any unsupported combination is refused before anything is loaded (the list in main()):
+//   LCB_DEVICE=i / LCB_GPUS=N  the GPU (default 0; HIP_VISIBLE_DEVICES also applies), or HIP devices 0..N-1 driven from this process
+//   LCB_SEEDS=host|device      where the seeds are enumerated: host threads, or the device's own tables
+//   LCB_TABLES=host|device     where the device's tables are computed (device: one GPU)
+//   LCB_JUNCTIONS=file|device  the way to the graph: the junction file of --graph, or lcb_graph_build - the junctions come from the
+//                              FASTA arguments on the GPU, --graph is still required by the parser but never opened
+//   LCB_HANDOVER=host|device   the way the graph reaches the device: the graph build releases the GPU and the device uploads its tables, or
+//                              lcb_open_fasta - needs LCB_JUNCTIONS=device and one GPU: the graph's arrays stay in HBM and become the tables
+//   LCB_LOAD=host|device       where the junction file is read: lcb_graph_load on host threads, or lcb_open_junctions - needs
+//                              LCB_JUNCTIONS=file and one GPU: the file goes up as it is and graph and device come from one call
+// Which of the four opening calls runs is one value of `Opening`, chosen in one place.
 // The block finder itself runs on the MI355X through the C ABI in include/lcb.h.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lcb.h"
@@ -108,88 +112,81 @@ Args parse(int argc, char** argv)
     return a;
 }
 
+// An environment variable's value; unset and empty are the same: null.
+const char* env(const char* name)
+{
+    const char* v = getenv(name);
+    return v && *v ? v : nullptr;
+}
+int deviceOrdinal() { return env("LCB_DEVICE") ? atoi(env("LCB_DEVICE")) : 0; }
+int gpuCount() { return env("LCB_GPUS") ? atoi(env("LCB_GPUS")) : 1; }
+
+// One switch of the environment with two values: `def` (also when unset or empty) and `other`.
+struct Route {
+    bool other = false;       // it says `other`
+    std::string error;        // it says something else: the line to refuse it with
+};
+Route route(const char* name, const char* def, const char* other)
+{
+    Route r;
+    const std::string v = env(name) ? env(name) : def;
+    r.other = v == other;
+    if (!r.other && v != def) r.error = std::string("error: ") + name + " is '" + v + "': it is " + def + " (the default) or " + other;
+    return r;
+}
+
+// How graph and device come to be. A new way is a value here, a line in the choice and a case in the switch of main().
+enum Opening {
+    OPEN_LOAD,          // lcb_graph_load: the junction file of --graph, read on host threads
+    OPEN_GRAPH_BUILD,   // lcb_graph_build (LCB_JUNCTIONS=device): the junctions come from the FASTA files on the GPU, the graph is a host object
+    OPEN_FASTA,         // lcb_open_fasta (+ LCB_HANDOVER=device): the same, and the graph's arrays stay in HBM as the device's tables
+    OPEN_JUNCTIONS      // lcb_open_junctions (LCB_LOAD=device): the junction file goes up as it is, graph and device come from one call
+};
+
+// LCB_VERBOSE: what the two one-call routes report alike, in front of and behind the times that are their own
+void openCounts(const lcb_open_stats& os)
+{
+    std::cerr << " raw=" << os.graph.raw_occurrences << " kept=" << os.graph.kept_occurrences << " vertices=" << os.graph.vertices << " patched=" << os.graph.patched
+              << " download_bytes=" << os.graph.download_bytes << " upload_bytes=" << os.tables.upload_bytes << " csr_download_bytes=" << os.csr_download_bytes
+              << " peak_device_bytes=" << os.peak_device_bytes;
+}
+void openTimes(const lcb_open_stats& os)
+{
+    std::cerr << " compact_ms=" << os.graph.compact_ms << " place_ms=" << os.place_ms << " download_ms=" << os.graph.download_ms << " patch_ms=" << os.patch_ms
+              << " window_ms=" << os.tables.window_ms << " csr_ms=" << os.tables.csr_ms << " sort_ms=" << os.tables.sort_ms << " csr_download_ms=" << os.csr_download_ms
+              << " gather_ms=" << os.tables.gather_ms << std::endl;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
     const Args a = parse(argc, argv);
-    // where the seeds are enumerated: chosen like the GPU, from the environment; refused before anything is loaded
-    const char* seedsEnv = getenv("LCB_SEEDS");
-    const std::string seedRoute = seedsEnv && *seedsEnv ? seedsEnv : "host";
-    if (seedRoute != "host" && seedRoute != "device") {
-        std::cerr << "error: LCB_SEEDS is '" << seedRoute << "': it is host (the default) or device" << std::endl;
-        return 1;
-    }
-    const bool deviceSeeds = seedRoute == "device";
-    // ... and where the device's tables are computed (LCB_TABLES=host, the default, or device), the same way
-    const char* tablesEnv = getenv("LCB_TABLES");
-    const std::string tableRoute = tablesEnv && *tablesEnv ? tablesEnv : "host";
-    if (tableRoute != "host" && tableRoute != "device") {
-        std::cerr << "error: LCB_TABLES is '" << tableRoute << "': it is host (the default) or device" << std::endl;
-        return 1;
-    }
-    const bool deviceTables = tableRoute == "device";
-    // ... and the way to the graph (LCB_JUNCTIONS=file, the default, or device)
-    const char* junctionsEnv = getenv("LCB_JUNCTIONS");
-    const std::string junctionRoute = junctionsEnv && *junctionsEnv ? junctionsEnv : "file";
-    if (junctionRoute != "file" && junctionRoute != "device") {
-        std::cerr << "error: LCB_JUNCTIONS is '" << junctionRoute << "': it is file (the default) or device" << std::endl;
-        return 1;
-    }
-    const bool deviceJunctions = junctionRoute == "device";
-    {
-        const char* gpus = getenv("LCB_GPUS");
-        if (deviceTables && gpus && *gpus && atoi(gpus) > 1) {
-            std::cerr << "error: LCB_TABLES=device together with LCB_GPUS=" << gpus << " is not supported: the tables are built on the device of a single-GPU run (LCB_GPUS unset or 1)" << std::endl;
-            return 1;
-        }
-    }
-    // ... and the way the graph reaches the device (LCB_HANDOVER=host, the default, or device: one call from the FASTA files to graph and device)
-    const char* handoverEnv = getenv("LCB_HANDOVER");
-    const std::string handoverRoute = handoverEnv && *handoverEnv ? handoverEnv : "host";
-    if (handoverRoute != "host" && handoverRoute != "device") {
-        std::cerr << "error: LCB_HANDOVER is '" << handoverRoute << "': it is host (the default) or device" << std::endl;
-        return 1;
-    }
-    const bool deviceHandover = handoverRoute == "device";
-    if (deviceHandover) {
-        const char* gpus = getenv("LCB_GPUS");
-        if (!deviceJunctions) {
-            std::cerr << "error: LCB_HANDOVER=device requires LCB_JUNCTIONS=device: it is the graph built on the device that is handed over" << std::endl;
-            return 1;
-        }
-        if (tablesEnv && *tablesEnv && !deviceTables) {
-            std::cerr << "error: LCB_HANDOVER=device together with LCB_TABLES=host is not supported: the tables of a handed-over graph are built on the device (LCB_TABLES unset or device)" << std::endl;
-            return 1;
-        }
-        if (gpus && *gpus && atoi(gpus) > 1) {
-            std::cerr << "error: LCB_HANDOVER=device together with LCB_GPUS=" << gpus << " is not supported: the graph is handed over to the device of a single-GPU run (LCB_GPUS unset or 1)" << std::endl;
-            return 1;
-        }
-    }
-    // ... and where the junction file of --graph is read (LCB_LOAD=host, the default, or device: one call from the file to graph and device)
-    const char* loadEnv = getenv("LCB_LOAD");
-    const std::string loadRoute = loadEnv && *loadEnv ? loadEnv : "host";
-    if (loadRoute != "host" && loadRoute != "device") {
-        std::cerr << "error: LCB_LOAD is '" << loadRoute << "': it is host (the default) or device" << std::endl;
-        return 1;
-    }
-    const bool deviceLoad = loadRoute == "device";
-    if (deviceLoad) {
-        const char* gpus = getenv("LCB_GPUS");
-        if (deviceJunctions) {
-            std::cerr << "error: LCB_LOAD=device together with LCB_JUNCTIONS=device is not supported: there is no file to load (the junctions come from the FASTA files)" << std::endl;
-            return 1;
-        }
-        if (tablesEnv && *tablesEnv && !deviceTables) {
-            std::cerr << "error: LCB_LOAD=device together with LCB_TABLES=host is not supported: the tables of a graph opened on the device are built there (LCB_TABLES unset or device)" << std::endl;
-            return 1;
-        }
-        if (gpus && *gpus && atoi(gpus) > 1) {
-            std::cerr << "error: LCB_LOAD=device together with LCB_GPUS=" << gpus << " is not supported: the file is opened on the device of a single-GPU run (LCB_GPUS unset or 1)" << std::endl;
-            return 1;
-        }
-    }
+    // The routes are chosen like the GPU, from the environment, and what is wrong with them is said before anything is loaded: the
+    // first line of this list whose condition holds (the order is part of the tool's behaviour).
+    const Route seedsRoute = route("LCB_SEEDS", "host", "device"), tablesRoute = route("LCB_TABLES", "host", "device"), junctionsRoute = route("LCB_JUNCTIONS", "file", "device"),
+                handoverRoute = route("LCB_HANDOVER", "host", "device"), loadRoute = route("LCB_LOAD", "host", "device");
+    const bool tablesHost = env("LCB_TABLES") && !tablesRoute.other;      // said, not defaulted
+    const int nGpus = gpuCount();
+    const std::string gpus = std::string("LCB_GPUS=") + (env("LCB_GPUS") ? env("LCB_GPUS") : "");
+    const std::pair<bool, std::string> refusals[] = {
+        {!seedsRoute.error.empty(), seedsRoute.error},
+        {!tablesRoute.error.empty(), tablesRoute.error},
+        {!junctionsRoute.error.empty(), junctionsRoute.error},
+        {tablesRoute.other && nGpus > 1, "error: LCB_TABLES=device together with " + gpus + " is not supported: the tables are built on the device of a single-GPU run (LCB_GPUS unset or 1)"},
+        {!handoverRoute.error.empty(), handoverRoute.error},
+        {handoverRoute.other && !junctionsRoute.other, "error: LCB_HANDOVER=device requires LCB_JUNCTIONS=device: it is the graph built on the device that is handed over"},
+        {handoverRoute.other && tablesHost, "error: LCB_HANDOVER=device together with LCB_TABLES=host is not supported: the tables of a handed-over graph are built on the device (LCB_TABLES unset or device)"},
+        {handoverRoute.other && nGpus > 1, "error: LCB_HANDOVER=device together with " + gpus + " is not supported: the graph is handed over to the device of a single-GPU run (LCB_GPUS unset or 1)"},
+        {!loadRoute.error.empty(), loadRoute.error},
+        {loadRoute.other && junctionsRoute.other, "error: LCB_LOAD=device together with LCB_JUNCTIONS=device is not supported: there is no file to load (the junctions come from the FASTA files)"},
+        {loadRoute.other && tablesHost, "error: LCB_LOAD=device together with LCB_TABLES=host is not supported: the tables of a graph opened on the device are built there (LCB_TABLES unset or device)"},
+        {loadRoute.other && nGpus > 1, "error: LCB_LOAD=device together with " + gpus + " is not supported: the file is opened on the device of a single-GPU run (LCB_GPUS unset or 1)"},
+    };
+    for (const auto& r : refusals)
+        if (r.first) { std::cerr << r.second << std::endl; return 1; }
+    const bool deviceSeeds = seedsRoute.other, deviceTables = tablesRoute.other;
+    const Opening opening = handoverRoute.other ? OPEN_FASTA : junctionsRoute.other ? OPEN_GRAPH_BUILD : loadRoute.other ? OPEN_JUNCTIONS : OPEN_LOAD;
     lcb_graph* g = nullptr;
     lcb_device* dev = nullptr;
     lcb_gpus* set = nullptr;
@@ -201,58 +198,58 @@ int main(int argc, char** argv)
         std::cout << "Loading the graph..." << std::endl;                                      // sibeliaz.cpp:124
         std::vector<const char*> fa;
         for (auto& f : a.fasta) fa.push_back(f.c_str());
+        const int nFa = (int)fa.size(), k = (int)a.k, abundance = (int)a.a, threads = (int)a.t;
         lcb_params p;
         p.k = (int)a.k; p.min_block = (int)a.m; p.max_branch = (int)a.b; p.max_flank = (int)a.b;   // sibeliaz.cpp:133-138
         p.looking_depth = 8; p.phase_size = 256;
-        if (deviceHandover) {
-            // graph and device in one call, on LCB_DEVICE: the device exists from here on, createDevices below finds it made
-            const char* ordEnv = getenv("LCB_DEVICE");
-            lcb_open_stats os;
-            if (lcb_open_fasta(fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t, &p, ordEnv && *ordEnv ? atoi(ordEnv) : 0, nullptr, nullptr, &g, &dev, &os) != LCB_OK) { fail(); break; }
-            if (getenv("LCB_VERBOSE"))
-                std::cerr << "lcb: handover=device records=" << os.graph.junctions.base.records << " raw=" << os.graph.raw_occurrences << " kept=" << os.graph.kept_occurrences
-                          << " vertices=" << os.graph.vertices << " patched=" << os.graph.patched << " download_bytes=" << os.graph.download_bytes << " upload_bytes=" << os.tables.upload_bytes
-                          << " csr_download_bytes=" << os.csr_download_bytes << " peak_device_bytes=" << os.peak_device_bytes << " parse_ms=" << os.graph.parse_ms
-                          << " compact_ms=" << os.graph.compact_ms << " place_ms=" << os.place_ms << " download_ms=" << os.graph.download_ms << " patch_ms=" << os.patch_ms
-                          << " window_ms=" << os.tables.window_ms << " csr_ms=" << os.tables.csr_ms << " sort_ms=" << os.tables.sort_ms << " csr_download_ms=" << os.csr_download_ms
-                          << " gather_ms=" << os.tables.gather_ms << std::endl;
-        } else if (deviceJunctions) {
+        const bool verbose = getenv("LCB_VERBOSE") != nullptr;
+        lcb_open_stats os;
+        lcb_graph_build_stats gs;
+        bool opened = false;
+        switch (opening) {
+        case OPEN_LOAD:
+            g = lcb_graph_load(a.graph.c_str(), fa.data(), nFa, k, abundance, threads);
+            opened = g != nullptr;
+            break;
+        case OPEN_GRAPH_BUILD:
             // on LCB_DEVICE (device 0 of an LCB_GPUS=N set); the graph is a host object and the build has released the device when it returns
-            const char* ordEnv = getenv("LCB_DEVICE");
-            const char* setEnv = getenv("LCB_GPUS");
-            const bool several = setEnv && *setEnv && atoi(setEnv) > 1;
-            lcb_graph_build_stats gs;
-            g = lcb_graph_build(fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t, !several && ordEnv && *ordEnv ? atoi(ordEnv) : 0, nullptr, &gs);
-            if (g && getenv("LCB_VERBOSE"))
+            g = lcb_graph_build(fa.data(), nFa, k, abundance, threads, nGpus > 1 ? 0 : deviceOrdinal(), nullptr, &gs);
+            opened = g != nullptr;
+            if (opened && verbose)
                 std::cerr << "lcb: graph=device records=" << gs.junctions.base.records << " raw=" << gs.raw_occurrences << " kept=" << gs.kept_occurrences << " vertices=" << gs.vertices
                           << " patched=" << gs.patched << " partitions=" << gs.junctions.partitions << " download_bytes=" << gs.download_bytes << " peak_device_bytes="
                           << gs.peak_device_bytes << " parse_ms=" << gs.parse_ms << " upload_ms=" << gs.junctions.base.upload_ms << " insert_ms=" << gs.junctions.base.insert_ms
                           << " mark_ms=" << gs.junctions.mark_ms << " count_ms=" << gs.count_ms << " emit_ms=" << gs.junctions.base.emit_ms << " take_ms=" << gs.take_ms
                           << " abundance_ms=" << gs.abundance_ms << " compact_ms=" << gs.compact_ms << " download_ms=" << gs.download_ms << " csr_ms=" << gs.csr_ms << std::endl;
-        } else if (deviceLoad) {
+            break;
+        case OPEN_FASTA:
+            // graph and device in one call, on LCB_DEVICE: the device exists from here on, createDevices below finds it made
+            opened = lcb_open_fasta(fa.data(), nFa, k, abundance, threads, &p, deviceOrdinal(), nullptr, nullptr, &g, &dev, &os) == LCB_OK;
+            if (opened && verbose) {
+                std::cerr << "lcb: handover=device records=" << os.graph.junctions.base.records;
+                openCounts(os);
+                std::cerr << " parse_ms=" << os.graph.parse_ms;
+                openTimes(os);
+            }
+            break;
+        case OPEN_JUNCTIONS:
             // the junction file, opened on LCB_DEVICE: graph and device in one call, as with LCB_HANDOVER=device
-            const char* ordEnv = getenv("LCB_DEVICE");
-            lcb_open_stats os;
-            if (lcb_open_junctions(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t, &p, ordEnv && *ordEnv ? atoi(ordEnv) : 0, nullptr, nullptr, &g, &dev, &os) != LCB_OK) { fail(); break; }
-            if (getenv("LCB_VERBOSE"))
-                std::cerr << "lcb: load=device chromosomes=" << os.graph.junctions.base.records << " tiles=" << os.graph.junctions.base.tiles << " raw=" << os.graph.raw_occurrences
-                          << " kept=" << os.graph.kept_occurrences << " vertices=" << os.graph.vertices << " patched=" << os.graph.patched << " download_bytes=" << os.graph.download_bytes
-                          << " upload_bytes=" << os.tables.upload_bytes << " csr_download_bytes=" << os.csr_download_bytes << " peak_device_bytes=" << os.peak_device_bytes
-                          << " read_ms=" << os.graph.junctions.base.read_ms << " upload_ms=" << os.graph.junctions.base.upload_ms << " take_ms=" << os.graph.take_ms
-                          << " parse_ms=" << os.graph.parse_ms << " abundance_ms=" << os.graph.abundance_ms << " compact_ms=" << os.graph.compact_ms << " place_ms=" << os.place_ms
-                          << " download_ms=" << os.graph.download_ms << " patch_ms=" << os.patch_ms << " window_ms=" << os.tables.window_ms << " csr_ms=" << os.tables.csr_ms
-                          << " sort_ms=" << os.tables.sort_ms << " csr_download_ms=" << os.csr_download_ms << " gather_ms=" << os.tables.gather_ms << std::endl;
-        } else
-            g = lcb_graph_load(a.graph.c_str(), fa.data(), (int)fa.size(), (int)a.k, (int)a.a, (int)a.t);
-        if (!g) { fail(); break; }
+            opened = lcb_open_junctions(a.graph.c_str(), fa.data(), nFa, k, abundance, threads, &p, deviceOrdinal(), nullptr, nullptr, &g, &dev, &os) == LCB_OK;
+            if (opened && verbose) {
+                std::cerr << "lcb: load=device chromosomes=" << os.graph.junctions.base.records << " tiles=" << os.graph.junctions.base.tiles;
+                openCounts(os);
+                std::cerr << " read_ms=" << os.graph.junctions.base.read_ms << " upload_ms=" << os.graph.junctions.base.upload_ms << " take_ms=" << os.graph.take_ms
+                          << " parse_ms=" << os.graph.parse_ms << " abundance_ms=" << os.graph.abundance_ms;
+                openTimes(os);
+            }
+            break;
+        }
+        if (!opened) { fail(); break; }
         std::cout << "Analyzing the graph..." << std::endl;                                    // sibeliaz.cpp:132
         // GPU selection comes from the environment, never from argv (the wrapper's command line, sibeliaz:146, stays as it is):
         // LCB_GPUS=N uses HIP devices 0..N-1 (as filtered by HIP_VISIBLE_DEVICES), LCB_DEVICE=i uses device i; default one GPU.
         // So does the seed route: LCB_SEEDS=host (default) enumerates with -t host threads before the device exists, LCB_SEEDS=device
         // creates the device first and enumerates on its tables (with LCB_GPUS=N on device 0 of the set).
-        const char* devEnv = getenv("LCB_DEVICE");
-        const char* gpusEnv = getenv("LCB_GPUS");
-        const int nGpus = gpusEnv && *gpusEnv ? atoi(gpusEnv) : 1;
         auto createDevices = [&]() -> bool {
             if (dev) return true;             // (LCB_HANDOVER=device: made with the graph)
             if (nGpus > 1) {
@@ -263,9 +260,9 @@ int main(int argc, char** argv)
                 return set != nullptr;
             }
             lcb_table_stats ts;
-            dev = lcb_device_create_tables(g, &p, devEnv && *devEnv ? atoi(devEnv) : 0, nullptr, deviceTables ? LCB_TABLES_DEVICE : LCB_TABLES_HOST, &ts);
+            dev = lcb_device_create_tables(g, &p, deviceOrdinal(), nullptr, deviceTables ? LCB_TABLES_DEVICE : LCB_TABLES_HOST, &ts);
             if (dev && getenv("LCB_VERBOSE"))
-                std::cerr << "lcb: device tables=" << tableRoute << " positions=" << ts.positions << " vertices=" << ts.vertices << " sort_passes=" << ts.sort_passes << " (+"
+                std::cerr << "lcb: device tables=" << (deviceTables ? "device" : "host") << " positions=" << ts.positions << " vertices=" << ts.vertices << " sort_passes=" << ts.sort_passes << " (+"
                           << ts.sort_passes_skipped << " skipped) upload_bytes=" << ts.upload_bytes << " device_bytes=" << ts.device_bytes << " upload_ms=" << ts.upload_ms
                           << " window_ms=" << ts.window_ms << " csr_ms=" << ts.csr_ms << " sort_ms=" << ts.sort_ms << " gather_ms=" << ts.gather_ms << std::endl;
             return dev != nullptr;

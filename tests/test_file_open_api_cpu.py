@@ -12,18 +12,9 @@ import pytest
 import sibeliaz_amd
 from sibeliaz_amd import api
 from tests import file_inputs
+from tests.cli_inputs import cli as _cli, has_gpu as _has_gpu, refused as _refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "sibeliaz_amd", "bin", "sibeliaz-lcb")
-SWITCHES = ("LCB_LOAD", "LCB_HANDOVER", "LCB_JUNCTIONS", "LCB_TABLES", "LCB_SEEDS", "LCB_GPUS")
-
-
-def _has_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except ImportError:
-        return False
 
 
 def test_binding_and_header_agree_on_the_new_surface(built, tmp_path):
@@ -131,19 +122,6 @@ def test_both_calls_fail_loudly_without_a_gpu(built, tmp_path):
     for seeds in ("host", "device"):
         r = _cli(c["graph"], c["fasta"][0], tmp_path / "out", LCB_LOAD="device", LCB_SEEDS=seeds)
         assert r.returncode == 1 and r.stdout == "Loading the graph...\n" and "lcb_open_junctions" in r.stderr and "no HIP device" in r.stderr
-
-
-def _cli(graph, fasta, out, **env):
-    e = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-    e.update(env)
-    return subprocess.run([EXE, "--graph", graph, fasta, "-k", "15", "-o", str(out)], capture_output=True, text=True, env=e)
-
-
-def _refused(tmp_path, line, **env):
-    out = tmp_path / "out"
-    r = _cli(str(tmp_path / "no.bin"), str(tmp_path / "no.fa"), out, **env)
-    assert r.returncode == 1 and r.stderr == line + "\n", r.stderr
-    assert r.stdout == "" and not out.exists()
 
 
 @pytest.mark.parametrize("value", ["x", "Device", "gpu", "Host", "file", "hbm"])

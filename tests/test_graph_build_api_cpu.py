@@ -11,17 +11,9 @@ import pytest
 
 import sibeliaz_amd
 from sibeliaz_amd import api
+from tests.cli_inputs import cli as _cli, has_gpu as _has_gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "sibeliaz_amd", "bin", "sibeliaz-lcb")
-
-
-def _has_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except ImportError:
-        return False
 
 
 def test_binding_and_header_agree_on_the_new_surface(built, tmp_path):
@@ -85,12 +77,6 @@ def test_python_refuses_unknown_options_before_anything_is_created(built, tmp_pa
     for name in ("table_bits", "tiles", "reserved", "abundances"):
         with pytest.raises(TypeError, match=name):
             sibeliaz_amd.JunctionStorage.build([missing], 15, **{name: 3})
-
-
-def _cli(graph, fasta, out, **env):
-    e = {k: v for k, v in os.environ.items() if k != "LCB_JUNCTIONS"}
-    e.update(env)
-    return subprocess.run([EXE, "--graph", graph, fasta, "-k", "15", "-o", str(out)], capture_output=True, text=True, env=e)
 
 
 @pytest.mark.parametrize("value", ["x", "Device", "gpu", "File", "host"])

@@ -11,10 +11,9 @@ import pytest
 
 import sibeliaz_amd
 from sibeliaz_amd import api
-from tests import seed_inputs
+from tests import cli_inputs, seed_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "sibeliaz_amd", "bin", "sibeliaz-lcb")
 
 
 def test_binding_knows_the_new_entry_points(built, tmp_path):
@@ -57,9 +56,7 @@ def test_find_blocks_rejects_an_unknown_seeds_spelling(built, case):
 @pytest.mark.parametrize("value", ["bogus", "Device", "gpu"])
 def test_cli_rejects_an_unknown_seed_route_before_loading(built, case, tmp_path, value):
     out = tmp_path / "out"
-    env = dict(os.environ, LCB_SEEDS=value)
-    r = subprocess.run([EXE, "--graph", case.graph, case.fasta, "-k", str(case.k), "-b", str(case.b), "-m", str(case.m), "-a", str(case.a), "-o", str(out)],
-                       capture_output=True, text=True, env=env)
+    r = cli_inputs.cli(case.graph, case.fasta, out, args=("-k", str(case.k), "-b", str(case.b), "-m", str(case.m), "-a", str(case.a)), LCB_SEEDS=value)
     assert r.returncode == 1
     assert r.stderr.startswith("error:") and "LCB_SEEDS" in r.stderr and value in r.stderr
     assert r.stdout == "" and not out.exists()

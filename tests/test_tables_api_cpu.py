@@ -12,10 +12,9 @@ import pytest
 
 import sibeliaz_amd
 from sibeliaz_amd import api
-from tests import table_inputs
+from tests import cli_inputs, table_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "sibeliaz_amd", "bin", "sibeliaz-lcb")
 
 
 def test_binding_and_header_agree_on_the_new_surface(built, tmp_path):
@@ -57,9 +56,18 @@ def test_python_refuses_an_unknown_tables_spelling_before_anything_is_created(bu
             sibeliaz_amd.Device(Untouchable(), sibeliaz_amd.Params.make(15), 0, tables=spelling)
 
 
+def test_python_refuses_an_unknown_device_option_wherever_one_is_taken(built):
+    class Untouchable:          # any use of the storage would be an AttributeError, not a TypeError
+        pass
+    p = sibeliaz_amd.Params.make(15)
+    for make in (lambda: sibeliaz_amd.Device(Untouchable(), p, 0, seg_caps=64), lambda: sibeliaz_amd.GpuSet(Untouchable(), p, [0], seg_caps=64),
+                 lambda: sibeliaz_amd.BlocksFinder(Untouchable(), 15).FindBlocksGpus(50, 200, [0], device_opts=dict(seg_caps=64))):
+        with pytest.raises(TypeError, match="unknown device option 'seg_caps'"):
+            make()
+
+
 def _cli(case, out, **env):
-    return subprocess.run([EXE, "--graph", case.graph, case.fasta, "-k", str(case.k), "-b", str(case.b), "-m", str(case.m), "-a", str(case.a), "-o", str(out)],
-                          capture_output=True, text=True, env=dict(os.environ, **env))
+    return cli_inputs.cli(case.graph, case.fasta, out, args=("-k", str(case.k), "-b", str(case.b), "-m", str(case.m), "-a", str(case.a)), **env)
 
 
 @pytest.mark.parametrize("value", ["x", "Device", "gpu"])
