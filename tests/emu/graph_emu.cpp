@@ -4,6 +4,7 @@
 // <tile> windows), the code bytes are made from the strings of graph.cpp's parser. Take, abundance (both instantiations), keep-count,
 // scan, compaction, the host's patch and graph.cpp's CSR must give the graph lcb_graph_load_impl makes of the same file.
 //   graph_emu <junctions> <k> <abundance> <tile> <fasta> [<fasta> ...]
+//   graph_emu scan <n>          graphScan alone on generated arrays of n entries (every content of scan_cases.h), against a serial 64-bit prefix sum
 // Exit status 0 = equal; otherwise the first difference on stderr. tests/test_graph_emu.py runs it.
 #include <hip/hip_runtime.h>     // the shadow header of this directory
 
@@ -33,6 +34,7 @@ static inline int __popc(uint32_t x) { return __builtin_popcount(x); }
 #include "lcb_fasta.h"
 #include "lcb_graph_kernels.h"
 #include "lcb_host.h"
+#include "scan_cases.h"
 using namespace lcb_graphk;
 
 template <class F> void launch(uint64_t grid, int threads, F body) { for (uint64_t b = 0; b < grid; b++) emu_run_block((uint32_t)b, threads / 64, body); }
@@ -150,7 +152,10 @@ static int run(const char* junctions, int k, int abundance, uint64_t tile, const
 
 int main(int argc, char** argv)
 {
-    if (argc < 6) { fprintf(stderr, "usage: graph_emu <junctions> <k> <abundance> <tile> <fasta> [<fasta> ...]\n"); return 2; }
+    if (argc == 3 && std::string(argv[1]) == "scan")
+        return scanCheckAll<unsigned long long>("graphScan", strtoull(argv[2], nullptr, 10), 4ull * G_SCAN_T,
+                                                [](unsigned long long* a, uint64_t m, unsigned long long* t) { launch(1, G_SCAN_T, [&]() { graphScan(a, m, t); }); });
+    if (argc < 6) { fprintf(stderr, "usage: graph_emu <junctions> <k> <abundance> <tile> <fasta> [<fasta> ...] | graph_emu scan <n>\n"); return 2; }
     try {
         return run(argv[1], atoi(argv[2]), atoi(argv[3]), strtoull(argv[4], nullptr, 10), std::vector<std::string>(argv + 5, argv + argc));
     } catch (std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 2; }

@@ -1,8 +1,11 @@
 // tests/emu/junction_emu.cpp — TEST-ONLY: the kernels of the GPU junction finder (sibeliaz_amd/csrc/lcb_junction_kernels.h, unmodified) on the
 // lockstep wavefront emulator, driven like csrc/junctions.hip drives them (table regrowth, tiles in file order), writing the junction
 // file: junction_emu <k> <table_log2> <tile_windows> <out> <fasta...>. tests/test_junctions_emu.py compares it with lcb-mkgraph's.
+// junction_emu scan <nb>: junctionScan alone on generated counts (junction_emu_common.h); tests/test_scan_pieces_emu.py runs it.
 #include "junction_emu_common.h"
 int main(int argc, char** argv) {
+    if (argc == 3 && std::string(argv[1]) == "scan") return runJunctionScan((uint32_t)strtoul(argv[2], nullptr, 10));
+    if (argc < 6) { fprintf(stderr, "usage: junction_emu <k> <table_log2> <tile_windows> <out> <fasta...> | junction_emu scan <nb>\n"); return 2; }
     int k = atoi(argv[1]); uint32_t capLog2 = atoi(argv[2]); uint32_t tileWindows = atoi(argv[3]); std::string out = argv[4];
     const Input in(argv + 5, argv + argc);
     const uint64_t len = in.len;

@@ -67,4 +67,44 @@ template <class F> bool runTiles(const Input& in, uint32_t tileWindows, FILE* f,
     for (; curRec < in.recLen.size(); curRec++) put(0xFFFFFFFFu, INT64_MAX);
     return true;
 }
+
+// The `scan` mode: junctionScan alone on generated counts of nb workgroups (every content of scan_cases.h that 32-bit entries have), two
+// tiles in a row through one JState, against serial 64-bit prefix sums: every offset, totJ, totF, tileIdBase and idNext after each tile,
+// and the fields of JState that the kernel does not own. 0 = equal.
+#include "scan_cases.h"
+static int runJunctionScan(uint32_t nb) {
+    const uint32_t per = (nb + 1023) / 1024;
+    for (const char* content : SCAN_CONTENTS) {
+        std::vector<uint32_t> probe;
+        if (!scanFill(probe, nb, content, per, 0)) continue;
+        JState st;
+        memset(&st, 0, sizeof(st));
+        st.used = 77; st.idNext = 5; st.tileIdBase = 0xEEEE; st.totJ = st.totF = 0xEEEE;      // (ids given before; stale values of an earlier tile)
+        unsigned long long idNext = st.idNext;
+        for (int tile = 0; tile < 2; tile++) {
+            std::vector<uint32_t> cj, cf;
+            scanFill(cj, nb, content, per, 10 + 2 * tile);
+            scanFill(cf, nb, content, per, 11 + 2 * tile);
+            for (uint32_t q = 0; q < nb; q++) cf[q] = std::min(cf[q], cj[q]);      // first occurrences are junctions
+            std::vector<unsigned long long> wantJ, wantF;
+            const unsigned long long totJ = scanSerial(cj, wantJ), totF = scanSerial(cf, wantF);
+            cj.push_back(0xEEEEEEEEu); cf.push_back(0xEEEEEEEEu);
+            launch(1, 1024, [&]() { junctionScan(cj.data(), cf.data(), nb, &st); });
+            if (cj[nb] != 0xEEEEEEEEu || cf[nb] != 0xEEEEEEEEu) { fprintf(stderr, "junctionScan nb %u %s tile %d: the kernel wrote behind an array\n", nb, content, tile); return 1; }
+            for (uint32_t q = 0; q < nb; q++)
+                if (cj[q] != wantJ[q] || cf[q] != wantF[q]) {
+                    fprintf(stderr, "junctionScan nb %u %s tile %d: entry %u is (%u, %u), the serial scan has (%llu, %llu)\n", nb, content, tile, q, cj[q], cf[q], wantJ[q], wantF[q]);
+                    return 1;
+                }
+            if (st.totJ != totJ || st.totF != totF || st.tileIdBase != idNext || st.idNext != idNext + totF || st.used != 77 || st.full || st.lost) {
+                fprintf(stderr, "junctionScan nb %u %s tile %d: totJ %llu totF %llu tileIdBase %llu idNext %llu used %llu full %u lost %u, expected %llu %llu %llu %llu 77 0 0\n", nb, content, tile,
+                        st.totJ, st.totF, st.tileIdBase, st.idNext, st.used, st.full, st.lost, totJ, totF, idNext, idNext + totF);
+                return 1;
+            }
+            idNext += totF;
+            printf("scan junctionScan nb %u per %u %s tile %d totJ %llu totF %llu\n", nb, per, content, tile, totJ, totF);
+        }
+    }
+    return 0;
+}
 #endif

@@ -3,6 +3,8 @@
 //   seeds_emu enum <junctions> <fasta> <k> <abundance> [seg_cap seg_gap]   tables laid out as device.hip lays them out (lcb_segments.h);
 //                                                                          count, scan, fill, sort; compared field by field and in order
 //   seeds_emu sort <N> <pattern>                                           the sort kernels alone on generated keys, against std::sort
+//   seeds_emu scan <seedScan32|seedScan64> <n>                             one scan kernel alone on generated arrays of n entries (every content of
+//                                                                          scan_cases.h), against a serial 64-bit prefix sum
 // Exit status 0 = equal; otherwise the first difference on stderr. tests/test_seeds_emu.py runs both.
 #include <hip/hip_runtime.h>     // the shadow header of this directory
 
@@ -25,6 +27,7 @@ static inline unsigned long long atomicMin(unsigned long long* a, unsigned long 
 #include "lcb_host.h"
 #include "lcb_seed_kernels.h"
 #include "lcb_segments.h"
+#include "scan_cases.h"
 using namespace lcb_seedk;
 
 template <class F> void launch(uint32_t grid, int threads, F body) { emu_grid_x = grid; for (uint32_t b = 0; b < grid; b++) emu_run_block(b, threads / 64, body); }
@@ -151,12 +154,22 @@ static int runEnum(int argc, char** argv)
     return rc;
 }
 
+static int runScan(const std::string& kernel, unsigned long long n)
+{
+    if (kernel == "seedScan32") return scanCheckAll<uint32_t>("seedScan32", n, 4ull * S_SCAN_T, [](uint32_t* a, unsigned long long m, unsigned long long* t) { launch(1, S_SCAN_T, [&]() { seedScan32(a, m, t); }); });
+    // (a run of `per` consecutive entries per lane: the second lane's first entry stands for the second piece)
+    if (kernel == "seedScan64") return scanCheckAll<unsigned long long>("seedScan64", n, (n + S_SCAN_T - 1) / S_SCAN_T, [](unsigned long long* a, unsigned long long m, unsigned long long* t) { launch(1, S_SCAN_T, [&]() { seedScan64(a, m, t); }); });
+    fprintf(stderr, "unknown kernel %s\n", kernel.c_str());
+    return 2;
+}
+
 int main(int argc, char** argv)
 {
     try {
+        if (argc >= 4 && std::string(argv[1]) == "scan") return runScan(argv[2], strtoull(argv[3], nullptr, 10));
         if (argc >= 4 && std::string(argv[1]) == "sort") return runSort(strtoull(argv[2], nullptr, 10), argv[3]);
         if (argc >= 6 && std::string(argv[1]) == "enum") return runEnum(argc, argv);
     } catch (std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 2; }
-    fprintf(stderr, "usage: seeds_emu enum <junctions> <fasta> <k> <abundance> [seg_cap seg_gap] | seeds_emu sort <N> <pattern>\n");
+    fprintf(stderr, "usage: seeds_emu enum <junctions> <fasta> <k> <abundance> [seg_cap seg_gap] | seeds_emu sort <N> <pattern> | seeds_emu scan <kernel> <n>\n");
     return 2;
 }

@@ -3,6 +3,8 @@
 // lcb_window_table (lcb_segments.h), the graph's occStart and the occurrence records made from occG / occChr.
 //   tables_emu graph <junctions> <fasta> <k> <abundance> <max_branch> [seg_cap seg_gap]   a loaded graph, tables laid out as device.hip lays them out
 //   tables_emu edge <max_branch>                                                          a hand-made graph with positions at 0 and at 2^32 - 1
+//   tables_emu scan <tableScan32|tableScan64> <n>                                         one scan kernel alone on generated arrays of n entries (every
+//                                                                                         content of scan_cases.h), against a serial 64-bit prefix sum
 // Exit status 0 = equal; otherwise the first difference on stderr. tests/test_tables_emu.py runs both.
 #include <hip/hip_runtime.h>     // the shadow header of this directory
 
@@ -20,6 +22,7 @@ template <class V> static inline uint64_t emu_shfl_up(V v, int d, const char* f,
 #include "lcb_host.h"
 #include "lcb_segments.h"
 #include "lcb_table_kernels.h"
+#include "scan_cases.h"
 using namespace lcb_tablek;
 
 template <class F> void launch(uint64_t grid, int threads, F body) { for (uint64_t b = 0; b < grid; b++) emu_run_block((uint32_t)b, threads / 64, body); }
@@ -148,9 +151,21 @@ static lcb_graph edgeGraph()
     return g;
 }
 
+template <class Q> static int runScan(const char* kernel, uint64_t n)
+{
+    return scanCheckAll<Q>(kernel, n, 4ull * T_SCAN_T, [](Q* a, uint64_t m, unsigned long long* t) { launch(1, T_SCAN_T, [&]() { K<Q>::scan(a, m, t); }); });
+}
+
 int main(int argc, char** argv)
 {
     try {
+        if (argc >= 4 && std::string(argv[1]) == "scan") {
+            const uint64_t n = strtoull(argv[3], nullptr, 10);
+            if (std::string(argv[2]) == "tableScan32") return runScan<uint32_t>("tableScan32", n);
+            if (std::string(argv[2]) == "tableScan64") return runScan<unsigned long long>("tableScan64", n);
+            fprintf(stderr, "unknown kernel %s\n", argv[2]);
+            return 2;
+        }
         if (argc >= 7 && std::string(argv[1]) == "graph") {
             lcb_graph* g = lcb_graph_load_impl(argv[2], {argv[3]}, atoi(argv[4]), atoi(argv[5]), 2);
             const int rc = run(*g, (uint32_t)strtoul(argv[6], nullptr, 10), argc > 7 ? strtoull(argv[7], nullptr, 10) : 0, argc > 8 ? strtoull(argv[8], nullptr, 10) : 0);
@@ -164,6 +179,6 @@ int main(int argc, char** argv)
             return rc ? rc : run(g, mb, 12, 100);              // ... and cut into segments with a gap: the 64-bit instantiation
         }
     } catch (std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 2; }
-    fprintf(stderr, "usage: tables_emu graph <junctions> <fasta> <k> <abundance> <max_branch> [seg_cap seg_gap] | tables_emu edge <max_branch>\n");
+    fprintf(stderr, "usage: tables_emu graph <junctions> <fasta> <k> <abundance> <max_branch> [seg_cap seg_gap] | tables_emu edge <max_branch> | tables_emu scan <kernel> <n>\n");
     return 2;
 }

@@ -17,7 +17,9 @@ EMU = os.path.join(ROOT, "tests", "emu")
 CSRC = os.path.join(ROOT, "sibeliaz_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 TILE = 1024          # S_TILE of lcb_seed_kernels.h: the records of one workgroup of the scatter kernel (the harness prints it; checked below)
-SORT_SIZES = [0, 1, 2, TILE - 1, TILE, TILE + 1, 3 * TILE + 17]
+# seedScan32 walks the 256 histogram entries per tile in pieces of 4096: from 17 tiles on it takes a second piece (with exactly 17 the
+# piece boundary falls inside one digit's run of the digit-major array), 34 tiles take three
+SORT_SIZES = [0, 1, 2, TILE - 1, TILE, TILE + 1, 3 * TILE + 17, 16 * TILE, 16 * TILE + 1, 33 * TILE + 17]
 PATTERNS = ["random", "count_top", "chr_only", "rank_low", "rank_wrap", "count_equal"]
 
 
